@@ -11,7 +11,13 @@ MaxRecords / MaxLeaderEpoch are not pinned by BASELINE.json; the C oracle exhaus
 binding (279,753,922 distinct states, tests/golden/oracle_kip320_3_6_6_2.json), which is what
 the GPU count is checked against in the same run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it opens the engine, runs W warm-up steps, times K steps,
+writes what the last timed step returned when --dump-outputs is given, and prints the line (with the roofline block of the
+timed steps, computed from their own HIP events and the committed profiles).  --full adds every leg that takes runs of its
+own — orbit_counting, traces_kept, cold_start, baseline_configs, stretch_1gpu, cpu_baseline — and the device's clocks; the
+--no-* options pick among those legs.
 
 N = 1: the whole search runs on one GPU inside libkmc.so (kmc_run).
 N > 1 (launched by torch.distributed.run, one rank per GPU): the fingerprint space is
@@ -313,6 +319,34 @@ def run_single(c, steps, warmup, symmetry=False, table=None, frontier=None, keep
     return results, dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, r):
+    """--dump-outputs: what the last timed step handed its caller (a CheckResult: the verdict and the search's counts, nothing
+    that is a time or a capacity), as float64 arrays DIR/<name>.npy — every count is below 2^53, so float64 holds it exactly;
+    the 64-bit fingerprint of a violation goes in as two 32-bit halves.  The workload is fully determined by the model and
+    its constants (hash seed 0), so two builds given the same arguments must write the same files."""
+    import numpy as np
+    from kafka_specification_amd._native import VERDICTS
+    fp = int(getattr(r, "violation_fp", 0))
+    arrays = {
+        "counts": [r.distinct, r.generated, r.depth, r.queue_left, r.deadlock_states, getattr(r, "generated_repeats", 0),
+                   getattr(r, "orbit_representatives", 0)],
+        "verdict": [VERDICTS.index(r.verdict), r.violation_depth, fp >> 32, fp & 0xFFFFFFFF],
+        "levels": list(r.levels),
+        "action_generated": list(r.action_generated.values()),      # in the order of the model's disjuncts of Next
+        "violation_count": list(r.violation_count.values()),
+    }
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+
+
 def algorithmic_bytes_per_state(r):
     """A = 2*S + 8*g + 8 per distinct state (frontier read + write, g seen-set probes of 8 B, one 8-B claim).
     g is priced on generated - generated_repeats: TLC's "generated" counts a successor twice when two disjuncts of one binding
@@ -573,6 +607,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (verdict, counts, level sizes, generated "
+                         "per action) as DIR/<name>.npy, float64; the same arguments give the same files on every run")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the legs that take runs of their own (orbit_counting, traces_kept, cold_start, "
+                         "baseline_configs, stretch_1gpu, cpu_baseline; the --no-* options pick among them) and the device's clocks")
     ap.add_argument("--cpu-states", type=int, default=0,
                     help="cpu_baseline sample size in distinct states (default: 25 %% of the workload's reachable set; the "
                          "oracle stops after the BFS level that crosses it)")
@@ -586,7 +626,7 @@ def main():
     ap.add_argument("--symmetry", action="store_true",
                     help="the timed region runs the orbit-counting search (kmc_config.symmetry) instead of the plain one: for "
                          "profiling that kernel; the default line times the plain search and reports orbit counting beside it")
-    ap.add_argument("--no-orbit-counting", action="store_true", help="skip the orbit_counting leg of the default line")
+    ap.add_argument("--no-orbit-counting", action="store_true", help="skip the orbit_counting leg of the --full line")
     ap.add_argument("--no-traces-leg", action="store_true", help="skip the traces_kept leg (the headline with predecessors kept, as a CLI run keeps them)")
     ap.add_argument("--no-cold-start", action="store_true", help="skip the cold_start leg (one fresh CLI process, exec to exit)")
     ap.add_argument("--no-baseline-configs", action="store_true",
@@ -640,6 +680,8 @@ def main():
         return
 
     r = results[-1]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, r)
     distinct, generated = r.distinct, r.generated
     exp = expected_counts(c)
     counts_match = None if exp is None else (distinct == exp["distinct"] and generated == exp["generated"]
@@ -741,9 +783,12 @@ def main():
                              "(random_access.dram_traffic_frac_of_hbm_peak; ratio_to_randbench_same_mix ~ 1: the run moves "
                              "its lines as fast as a microbenchmark of the same load/CAS mix); neither fewer ALU instructions "
                              "nor more waves per SIMD shorten it (profiles/r02_ablation.txt, r02_occupancy_sweep.txt)"},
-        "device": device_info(),
     }
-    if (world == 1 and not a.symmetry and not a.no_orbit_counting and not a.level_budget and c["n_replicas"] <= KMC_SYMMETRY_MAX_REPLICAS
+    if a.full:
+        out["device"] = device_info()
+    # the legs beside the headline (--full): each is a run of its own
+    legs = a.full and world == 1
+    if (legs and not a.symmetry and not a.no_orbit_counting and not a.level_budget and c["n_replicas"] <= KMC_SYMMETRY_MAX_REPLICAS
             and r.verdict == "ok"):
         # The same check with symmetry reduction by orbit counting (kmc_config.symmetry): one stored
         # state per orbit of the permutations of Replicas, every count weighted by the orbit's size.  It must report the
@@ -773,7 +818,7 @@ def main():
                          "note": "algorithmic bytes of the STORED states (the same per-state figure) over this search's "
                                  "k_expand time; the kernel is instruction-bound here (the representative of every successor "
                                  "is the smallest of its images under the permutations: profiles/r03_symmetry.txt)"}}
-    if (world == 1 and not a.symmetry and not a.level_budget and not a.no_traces_leg and not a.workload and not a.small
+    if (legs and not a.symmetry and not a.level_budget and not a.no_traces_leg and not a.workload and not a.small
             and os.environ.get("KMC_BENCH_TRACE", "0") != "1" and r.verdict == "ok"):
         # The same check as a CLI user runs it: predecessors kept for counterexample traces (TLC always keeps them; `value` above
         # is the search alone, as BASELINE.json's metric is).  Since round 6 a claim's predecessor is the second word of the claim's
@@ -791,17 +836,17 @@ def main():
                 "seen_set": "16-byte slots: fingerprint + predecessor (kmc_handle::paired)"}
         except Exception as e:   # (a leg beside the headline never takes the line down)
             out["traces_kept"] = {"error": repr(e)}
-    if world == 1 and not a.symmetry and not a.level_budget and not a.no_cold_start:
+    if legs and not a.symmetry and not a.level_budget and not a.no_cold_start:
         # (before the legs with the large tables: the front-end process that started right after the stretch leg had handed its
         # 250 GiB back spent 0.26 - 0.35 s in its own teardown - calls 28 and 33 - against 0.02 - 0.05 s at any other time: what a CLI
         # user waits for is measured on a device that is not still digesting somebody else's release)
         cs = cold_start(c)
         if cs:
             out["cold_start"] = cs
-    if (world == 1 and not a.symmetry and not a.level_budget and not a.no_baseline_configs and not a.workload and not a.small):
+    if (legs and not a.symmetry and not a.level_budget and not a.no_baseline_configs and not a.workload and not a.small):
         # SURVEY section 8d rows "config 4" and "config 5": driver-timed here, never part of `value`
         out["baseline_configs"] = {name: baseline_leg(name, a.config_steps, 1, with_cpu=not a.no_cpu_baseline) for name in BASELINE_LEGS}
-    if (world == 1 and not a.symmetry and not a.level_budget and not a.no_stretch and not a.workload and not a.small):
+    if (legs and not a.symmetry and not a.level_budget and not a.no_stretch and not a.workload and not a.small):
         out["stretch_1gpu"] = stretch_1gpu_leg()
     if want_stretch:
         # The headline line is complete here.  The stretch leg is another collective search (6.45 G states over the ranks): should
@@ -809,7 +854,7 @@ def main():
         sys.stderr.write("[bench.py: the headline line, before the stretch leg] " + json.dumps(out) + "\n")
         sys.stderr.flush()
         out["stretch"] = stretch_leg(a)
-    if not a.no_cpu_baseline and world == 1:
+    if legs and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(c, a.cpu_states or max(1_000_000, distinct // 4), distinct)
     print(json.dumps(out))
 

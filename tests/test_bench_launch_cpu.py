@@ -24,9 +24,10 @@ def _run(args, extra_env=None, timeout=300):
                           env=env, timeout=timeout, cwd=ROOT)
 
 
-def test_bench_gpus2_self_launches_and_prints_one_line():
+def test_bench_gpus2_self_launches_and_prints_one_line(tmp_path):
+    dump = str(tmp_path / "outputs")
     p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline",
-              "--workload", "Kip320,2,2,2,2"], {"KMC_SHARD_ENGINE": "shard_standin:make_engine"})
+              "--workload", "Kip320,2,2,2,2", "--dump-outputs", dump], {"KMC_SHARD_ENGINE": "shard_standin:make_engine"})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout                       # rank 0 only
@@ -42,6 +43,14 @@ def test_bench_gpus2_self_launches_and_prints_one_line():
     assert r["config"]["pipelined_levels"] == 0 and "pipeline_min_states" in r["config"] and "pipeline_parts" in r["config"]
     assert r["value"] > 0 and r["ms_per_step"] > 0
     assert "cpu_baseline" not in r                         # N>1 lines carry no CPU leg
+    # --dump-outputs: what the last timed step returned, as float64 arrays (rank 0 writes them)
+    import numpy as np
+    got = {f[:-4]: np.load(os.path.join(dump, f)) for f in sorted(os.listdir(dump))}
+    assert sorted(got) == ["action_generated", "counts", "levels", "verdict", "violation_count"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert list(got["counts"][:3]) == [o.distinct, o.generated, o.depth] and got["verdict"][0] == 0
+    assert list(got["levels"]) == list(o.levels)
+    assert got["action_generated"].sum() == o.generated - o.levels[0]    # ("generated" counts the initial states too, as TLC's does)
 
 
 def test_bench_gpus2_stretch_leg_rides_beside_the_headline():

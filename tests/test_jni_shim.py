@@ -44,9 +44,10 @@ def build_harness():
     src = [os.path.join(ROOT, "tests", "jni_stub", "fake_jvm.c"), SRC]
     lib = os.path.join(ROOT, "kafka_specification_amd")
     if not os.path.exists(HARNESS) or any(os.path.getmtime(HARNESS) < os.path.getmtime(s) for s in src):
+        # (the run path is relative to the harness: a tree that was built in one place and is run in another finds its library)
         subprocess.check_call(["gcc", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "tests", "jni_stub"),
-                               "-I" + os.path.join(ROOT, "include"), *src, "-L" + lib, "-lkmc", "-Wl,-rpath," + lib,
-                               "-o", HARNESS])
+                               "-I" + os.path.join(ROOT, "include"), *src, "-L" + lib, "-lkmc",
+                               "-Wl,-rpath,$ORIGIN/../kafka_specification_amd", "-o", HARNESS])
     return HARNESS
 
 
