@@ -108,7 +108,9 @@ def precompile_variants():
     return [(small, {"KMC_VERIFY": "1"}), (wide, {"KMC_VERIFY": "1"}), (golden, {"KMC_VERIFY": "1"}), (small, fault),
             (small, dict(fault, KMC_VERIFY="1")),
             (dict(model="AsyncIsr", n_replicas=3, log_size=2, max_leader_epoch=2), fault),
-            (small, {"KMC_JIT_DEFINES": "-DKMC_TUNING=1 -DKMC_TEST_FP_BITS=10"})] + layout_variants() + symmetry_variants() + full_leaves_variants() + deferred_probe_variants()   # (collisions on demand for the wide-fingerprint test)
+            (small, {"KMC_JIT_DEFINES": "-DKMC_TUNING=1 -DKMC_TEST_FP_BITS=10"}),
+            # the device half of a tuning build (the dry kernel): tests/test_gpu_knobs_and_tuning_build.py runs libkmc_tuning.so on it
+            (small, {"KMC_JIT_DEFINES": "-DKMC_TUNING=1"})] + layout_variants() + symmetry_variants() + full_leaves_variants() + deferred_probe_variants()   # (collisions on demand for the wide-fingerprint test)
 
 
 # The arrangements of the Kafka state vector (csrc/kmc_layout.h) and the two walks of k_expand's pass 2 that go with them:

@@ -66,16 +66,15 @@ int64_t compiler_id_mine() {
 // The compiler whose objects every process prefers (KMC_PINNED_COMPILER: profiles/r06_compiler_ab.txt holds the A/B it was
 // chosen by; KMC_COMPILER_PIN=<id> overrides, 0 = no preference).
 int64_t compiler_id_pinned() {
-    if (const char* e = getenv("KMC_COMPILER_PIN")) return (int64_t)atoll(e);
-    return (int64_t)KMC_PINNED_COMPILER;
+    return (int64_t)env_int("KMC_COMPILER_PIN", KMC_PINNED_COMPILER);
 }
 
 // KMC_LAYOUT=tight|rm|rmg (tests, A/B measurements) overrides the automatic choice between the arrangements of the Kafka state
 // vector (kmc_layout.h); host and device evaluate the same constexpr function with the same mode.  A handle reads the
-// environment ONCE, at kmc_open (kmc_handle::layout_mode): its later code objects (ensure_mode) are specialised for the layout
+// environment ONCE, at kmc_open (kmc_knobs::layout_mode): its later code objects (ensure_mode) are specialised for the layout
 // it was opened with, whatever the environment says by then.
 int layout_mode_from_env() {
-    const char* lenv = getenv("KMC_LAYOUT");
+    const char* lenv = env_str("KMC_LAYOUT");
     return !lenv || !*lenv || !strcmp(lenv, "auto") ? KMC_LAYOUT_AUTO
            : !strcmp(lenv, "tight") ? KMC_LAYOUT_TIGHT : !strcmp(lenv, "rm") ? KMC_LAYOUT_RM
            : !strcmp(lenv, "rmg") ? KMC_LAYOUT_RMG : -1;
@@ -161,7 +160,7 @@ static std::string strip_for_concat(const char* src) {
 }
 
 static std::string default_cache_dir() {
-    if (const char* e = getenv("KMC_CACHE_DIR")) return e;
+    if (const char* e = env_str("KMC_CACHE_DIR")) return e;
     Dl_info info;
     if (dladdr((void*)&default_cache_dir, &info) && info.dli_fname) {
         std::string p = info.dli_fname;
@@ -230,7 +229,7 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     std::vector<std::string> defines;
     std::string defines_key;
     // (a handle's later code objects — ensure_mode — are built with the defines its first one was opened under: jit_defines)
-    std::string all_defines = jit_defines ? *jit_defines : getenv("KMC_JIT_DEFINES") ? getenv("KMC_JIT_DEFINES") : "";
+    std::string all_defines = jit_defines ? *jit_defines : env_str("KMC_JIT_DEFINES", "");
     if (extra_options) all_defines += std::string(" ") + extra_options;
     if (cfg.symmetry) all_defines += " -DKMC_SYMM=1";
     if (mode != KMC_MODE_LOCAL) all_defines += " -DKMC_ONLY_MODE=" + std::to_string(mode);
@@ -281,10 +280,11 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     const std::string path = path_of(mine);
     if (path_out) *path_out = path;
     if (read_file(path, code)) return KMC_OK;
-    if (getenv("KMC_VERBOSE") && pinned && pinned != mine)
+    const bool verbose = env_str("KMC_VERBOSE") != nullptr;
+    if (verbose && pinned && pinned != mine)
         fprintf(stderr, "[kmc] no code object of the pinned compiler %lld for %s in %s: compiling with this process's (%lld)\n", pinned,
                 name.c_str(), dir.c_str(), mine);
-    if (getenv("KMC_VERBOSE"))
+    if (verbose)
         fprintf(stderr, "[kmc] specialising kernels for %s (first use; wide configurations take minutes)\n", name.c_str());
 
     // k_expand is compiled for 6 waves/SIMD (80 VGPRs).  Wide configurations (7-8 replicas: hundreds of

@@ -22,8 +22,8 @@ int ensure_mode(kmc_handle* h, unsigned mode) {
     if (f) return KMC_OK;
     std::vector<char> code;
     std::string kname;
-    int rc = get_code_object(h->cfg, h->arch, &code, &kname, h->verify ? KMC_VERIFY_PRIMARY_OPTIONS : nullptr, nullptr, mode, &h->jit_defines,
-                             h->layout_mode);
+    int rc = get_code_object(h->cfg, h->arch, &code, &kname, h->knobs.verify ? KMC_VERIFY_PRIMARY_OPTIONS : nullptr, nullptr, mode,
+                             &h->knobs.jit_defines, h->knobs.layout_mode);
     if (rc) return rc;
     HIP_TRY(hipModuleLoadData(&mod, code.data()));
     HIP_TRY(hipModuleGetFunction(&f, mod, (std::string("kmc_expand") + MODE_SUFFIX[mode] + "_" + h->kname).c_str()));
@@ -36,9 +36,10 @@ int launch_expand(kmc_handle* h, unsigned mode, const KmcArgs& a, unsigned grid,
     int rc = ensure_mode(h, mode);
     if (rc) return rc;
     hipFunction_t f = verify ? h->f_expand_verify : mode == KMC_MODE_LOCAL ? h->f_expand : mode == KMC_MODE_SHARDED ? h->f_expand_sh
-                    : mode == KMC_MODE_ENUM ? h->f_expand_en : h->f_expand_dry;
+                    : mode == KMC_MODE_ENUM ? h->f_expand_en : tuning_dry_kernel(h);
     if (!f)
-        return fail(KMC_E_STATE, "k_expand's dry mode is only compiled into a tuning build (KMC_JIT_DEFINES=-DKMC_TUNING=1)");
+        return fail(KMC_E_STATE, "k_expand's dry mode needs both halves of a tuning build: the host's (libkmc_tuning.so) and the "
+                                 "device's (KMC_JIT_DEFINES=-DKMC_TUNING=1)");
     KmcArgs args = a;
     const bool meta = (args.flags & KMC_FLAG_TRACE) || mode == KMC_MODE_ENUM;   // k_expand carves its rings out of dynamic LDS
     if (meta) args.flags |= KMC_FLAG_META;
@@ -87,22 +88,38 @@ int launch_inv(kmc_handle* h, const KmcArgs& a, uint64_t n) {
 // = 16 / 32 the headline's k_expand is 28.4 - 29.2 in every process where the chunks as they come give 28.4 - 30.6 (call 38, same
 // box, interleaved; BASELINE config 4 16.8 - 17.0 against 16.9 - 18.6; = 4 is not enough).  It is NOT the default: owning 120 GiB
 // for a moment costs 0.3 - 3 s at open, and the driver wipes what is handed back - 1 - 3 s that land in this handle's close or
-// in the next process's allocations.  A search of seconds and more earns that back (KMC_SEEN_SET_SPREAD=16; bench.py's timed legs
-// set it and say so); the front end answering a 30 ms search does not.
+// in the next process's allocations.  A search of seconds and more earns that back (KMC_SEEN_SET_SPREAD=16); the front end answering
+// a 30 ms search does not, and bench.py does not set it.
 #ifndef KMC_SCATTER_CLUSTERS
 #define KMC_SCATTER_CLUSTERS 64
 #endif
-static int spread_factor(size_t need) {
-    static const int env = getenv("KMC_SEEN_SET_SPREAD") ? atoi(getenv("KMC_SEEN_SET_SPREAD")) : KMC_SEEN_SET_SPREAD_DEFAULT;
-    int f = env < 1 ? 1 : env > 64 ? 64 : env;
+static int spread_factor(const kmc_handle* h, size_t need) {
+    int f = h->knobs.seen_set_spread;
     size_t free_b = 0, total_b = 0;
     if (f > 1 && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
         while (f > 1 && (double)need * f > 0.8 * (double)free_b) --f;   // (the spacers live only until the table is mapped)
     return f;
 }
+// A range goes back: ONE hipMemUnmap over its thousands of mappings and, should that fail, chunk by chunk (every chunk is a mapping
+// of its own: what one call refuses as a whole the single ones may still give back); then the addresses.
+static void unmap_chunks(const kmc_handle* h, void* va, size_t bytes, size_t chunk) {
+    const hipError_t e = hipMemUnmap(va, bytes);
+    if (e == hipSuccess) return;
+    size_t kept = 0;
+    for (size_t at = 0; at < bytes; at += chunk) kept += hipMemUnmap((char*)va + at, chunk) != hipSuccess;
+    (void)hipGetLastError();
+    if (h->knobs.verbose)
+        fprintf(stderr, "[kmc] seen-set memory: hipMemUnmap of %zu bytes at %p failed (%s): unmapped chunk by chunk, %zu of %zu chunks stay mapped\n",
+                bytes, va, hipGetErrorString(e), kept, bytes / chunk);
+}
+static void free_addresses(const kmc_handle* h, void* va, size_t bytes) {
+    const hipError_t e = hipMemAddressFree(va, bytes);
+    if (e != hipSuccess && h->knobs.verbose)
+        fprintf(stderr, "[kmc] seen-set memory: hipMemAddressFree of %zu bytes at %p failed (%s)\n", bytes, va, hipGetErrorString(e));
+    if (e != hipSuccess) (void)hipGetLastError();
+}
 u64* seen_set_alloc(kmc_handle* h, size_t bytes, bool chunks) {
-    static const int lg_env = getenv("KMC_SEEN_SET_CHUNK_LOG2") ? atoi(getenv("KMC_SEEN_SET_CHUNK_LOG2")) : 23;
-    const int lg = chunks ? lg_env : 0;
+    const int lg = chunks ? h->knobs.seen_set_chunk_log2 : 0;
     void* va = nullptr;
     size_t total = 0, done = 0;
     if (lg > 0) {
@@ -125,7 +142,7 @@ u64* seen_set_alloc(kmc_handle* h, size_t bytes, bool chunks) {
             step = "hipMemAddressReserve";
             e = hipMemAddressReserve(&va, total, chunk, nullptr, 0);
             if (e != hipSuccess) va = nullptr;
-            const int spread = spread_factor(total);
+            const int spread = spread_factor(h, total);
             per_cluster = (n + KMC_SCATTER_CLUSTERS - 1) / KMC_SCATTER_CLUSTERS;
             spacer_bytes = spread > 1 && n >= 2 ? (size_t)(spread - 1) * per_cluster * chunk : 0;
         }
@@ -153,19 +170,19 @@ u64* seen_set_alloc(kmc_handle* h, size_t bytes, bool chunks) {
             e = hipMemSetAccess(va, total, &d, 1);
         }
         if (e == hipSuccess) {
-            h->mapped.emplace_back(va, total);
-            if (getenv("KMC_VERBOSE"))
+            h->mapped.push_back({va, total, chunk});
+            if (h->knobs.verbose)
                 fprintf(stderr, "[kmc] seen-set memory: %zu chunks of %zu MiB in clusters of %zu, %zu spacers of %.2f GiB between them, %.3f s\n", n,
                         chunk >> 20, per_cluster, spacers.size(), (double)spacer_bytes / (double)(1ull << 30), now_s() - t0);
             return (u64*)va;
         }
         // undo what was mapped and fall back
-        if (getenv("KMC_VERBOSE"))
+        if (h->knobs.verbose)
             fprintf(stderr, "[kmc] seen-set memory: %s failed after %zu of %zu bytes in chunks of %zu (%s): falling back to one hipMalloc\n",
                     step, done, total, chunk, hipGetErrorString(e));
         if (va) {
-            if (done) (void)hipMemUnmap(va, done);
-            (void)hipMemAddressFree(va, total);
+            if (done) unmap_chunks(h, va, done, chunk);
+            free_addresses(h, va, total);
         }
         (void)hipGetLastError();
     }
@@ -176,14 +193,14 @@ u64* seen_set_alloc(kmc_handle* h, size_t bytes, bool chunks) {
 void seen_set_free(kmc_handle* h, u64* p) {
     if (!p) return;
     for (size_t k = 0; k < h->mapped.size(); ++k)
-        if (h->mapped[k].first == (void*)p) {
+        if (h->mapped[k].base == (void*)p) {
             const double t0 = now_s();
-            (void)hipMemUnmap(p, h->mapped[k].second);
+            unmap_chunks(h, p, h->mapped[k].bytes, h->mapped[k].chunk);
             const double t1 = now_s();
-            (void)hipMemAddressFree(p, h->mapped[k].second);
-            if (getenv("KMC_VERBOSE"))
+            free_addresses(h, p, h->mapped[k].bytes);
+            if (h->knobs.verbose)
                 fprintf(stderr, "[kmc] released %.1f GiB of chunks: unmap %.3f s, address range %.3f s\n",
-                        (double)h->mapped[k].second / (double)(1ull << 30), t1 - t0, now_s() - t1);
+                        (double)h->mapped[k].bytes / (double)(1ull << 30), t1 - t0, now_s() - t1);
             h->mapped.erase(h->mapped.begin() + (long)k);
             return;
         }
@@ -233,7 +250,7 @@ unsigned expand_grid(kmc_handle* h, uint64_t n) {
     uint64_t blocks = (tiles + KMC_WAVES - 1) / KMC_WAVES;
     // one resident wave of blocks: more than the kernel's occupancy only queues blocks and
     // unbalances the tail (measured: 73 ms at 5 blocks/CU vs 59 ms at the resident 4)
-    static const int forced = getenv("KMC_BLOCKS_PER_CU") ? atoi(getenv("KMC_BLOCKS_PER_CU")) : 0;
+    const int forced = tuning_blocks_per_cu(h);
     const int per_cu = forced > 0 ? forced : h->blocks_per_cu;
     const uint64_t maxb = (uint64_t)h->n_cus * per_cu;
     if (blocks > maxb) blocks = maxb;
@@ -385,6 +402,31 @@ void book_level(kmc_handle* h, uint64_t produced, const KmcLevelCtl& c) {
     // stored states in a level, up to 5,039 per successor — they wrapped and `generated` came out 2^40 too large, found by
     // oracle/orbit_oracle.c.  A lane sees produced / (blocks x 256) states of a level: its sums stay below 2^26 for any level
     // the frontier can hold.)
+}
+
+// The part of kmc_run's loop that its chained and its level-by-level launches share.  (kmc_step_finish keeps its own: a shard
+// weighs and books a level that may be empty here and not elsewhere, and leaves the verdicts to its driver.)
+bool advance_level(kmc_handle* h, const KmcLevelCtl& c, double expand_ms, int* rc) {
+    kmc_result& r = h->res;
+    uint64_t new_seg[KMC_SEGS];
+    const uint64_t produced = produced_segments(h, c, new_seg);
+    const bool stop = absorb(h, c, h->frontier[h->cur], h->seg_n, rc);
+    if (*rc) return false;
+    if (stop) { r.queue_left = queue_now(h); return false; }   // invariant (the produced level is rolled back), deadlock, table / frontier full
+    note_level(h, c, h->n_cur, produced, expand_ms);
+    if (produced == 0) { h->n_cur = 0; return false; }
+    h->cur ^= 1;
+    h->n_cur = produced;
+    for (int sg = 0; sg < KMC_SEGS; ++sg) h->seg_n[sg] = new_seg[sg];
+    h->level++;
+    r.depth = h->level;
+    book_level(h, produced, c);
+    if ((double)r.orbit_representatives > KMC_TABLE_LOAD_LIMIT * (double)h->table_cap && r.verdict == KMC_V_OK) {
+        r.verdict = KMC_V_TABLE_FULL;
+        r.queue_left = queue_now(h);
+        return false;
+    }
+    return true;
 }
 
 int check_conservation(kmc_handle* h, const KmcLevelCtl& c, uint64_t inserted) {
@@ -556,7 +598,7 @@ Roctx* roctx() {
     static Roctx r;
     static std::once_flag once;
     std::call_once(once, [] {
-        const char* want = getenv("KMC_ROCTX");
+        const char* want = env_str("KMC_ROCTX");
         if (want && !atoi(want)) return;   // KMC_ROCTX=0: never
         // a profiler that traces markers has the library in the process already (RTLD_NOLOAD finds it); KMC_ROCTX=1 loads it
         const char* names[] = {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"};

@@ -36,7 +36,7 @@ struct KmcRccl {
 std::string g_rccl_error;   // why librccl could not be bound (dlerror() is read ONCE, where it happens: a second call returns NULL)
 
 void rccl_bind(KmcRccl& r) {
-    const char* names[] = {getenv("KMC_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+    const char* names[] = {env_str("KMC_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     for (const char* n : names) {
         if (!n || !*n) continue;
         if ((r.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;

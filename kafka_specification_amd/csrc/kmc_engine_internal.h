@@ -2,9 +2,10 @@
 // cache, a level's bookkeeping.  Nothing here is part of the C ABI (include/kmc.h); everything is hidden from the dynamic symbol
 // table of libkmc.so.
 //   kmc_engine_codeobj.cpp   validation of a configuration, the text handed to hiprtc, the on-disk cache, the register-budget rule
-//   kmc_engine_core.cpp      kernel launches, a level's counters folded into the result (absorb), conservation, Init
-//   kmc_engine_open.cpp      names, precompile, kmc_open / kmc_close, pack / unpack / fingerprint / representative of a state
+//   kmc_engine_core.cpp      kernel launches, the seen-set's memory, a level's counters folded into the result (absorb), the level entering the books (advance_level), conservation, Init
+//   kmc_engine_open.cpp      names, precompile, the handle's knobs (read_knobs), kmc_open / kmc_close, pack / unpack / fingerprint / representative of a state
 //   kmc_engine_run.cpp       kmc_run's level loop (chained launches), results, kmc_successors / kmc_check_states, traces
+//   kmc_engine_tuning.cpp    ONLY in libkmc_tuning.so (-DKMC_TUNING=1, as the device's tuning build): the dry / shadow passes and launch overrides behind the tuning_* hooks
 //   kmc_engine_step.cpp      checkpoint / recover, the level-step interface of one shard
 //   kmc_engine_exchange.cpp  the per-level exchange: RCCL bound with dlopen, the plan, one-shot and pipelined levels, logical shards
 // The engine stands in for TLC's ModelChecker + Worker threads [TLC-recall; TLC is not part of /root/reference].  No CPU fallback
@@ -35,7 +36,8 @@
 #pragma clang diagnostic pop
 
 // Levels kmc_run queues back to back before it waits (no progress callback): see run_levels.
-#define KMC_CHAIN 32
+#define KMC_CHAIN 32           // ... at the most: what a handle has events and control blocks for
+#define KMC_CHAIN_DEFAULT 16   // ... in a batch (a tuning build may ask for another: KMC_CHAIN_MAX)
 #define KMC_CTL_SLOTS (3 + KMC_CHAIN)   // two alternating levels + one auxiliary + one per chained level
 
 // KMC_VERIFY: both builds carry the fingerprint checksum (KMC_CHECKSUM, kmc_common.h); the second one differs in how it is
@@ -59,6 +61,31 @@
 
 #pragma GCC visibility push(hidden)
 
+// What the environment may change about a handle (README: "Environment the library honours"): read ONCE, by read_knobs at kmc_open —
+// its later code objects (ensure_mode) follow what it was opened under, a handle opened later follows what the environment says then.
+struct kmc_knobs {
+    bool verbose = false;                 // KMC_VERBOSE (set at all): where the seen-set's memory came from, what went back
+    bool verify = false;                  // KMC_VERIFY: the differential self-check against a second build of the kernels
+    std::string jit_defines;              // KMC_JIT_DEFINES
+    int layout_mode = KMC_LAYOUT_AUTO;    // KMC_LAYOUT (-1: not a layout's name)
+    int paired_slots = 1;                 // KMC_PAIRED_SLOTS: 0 never, 1 below KMC_DEFER_MIN_WORDS words, 2 always (open_impl)
+    int send_filter = -1;                 // KMC_SEND_FILTER: -1 unset (on for 2..4 shards), 0 off, 1 on
+    int seen_set_spread = 1;              // KMC_SEEN_SET_SPREAD, 1..64 (seen_set_alloc: spacers)
+    int seen_set_chunk_log2 = 23;         // KMC_SEEN_SET_CHUNK_LOG2: 0 = one hipMalloc (seen_set_alloc raises it to the granularity)
+};
+
+#if KMC_TUNING
+struct kmc_tuning {   // the tuning aids' part of a handle (kmc_engine_tuning.cpp; README: "Tuning build"): only libkmc_tuning.so has it
+    int shadow = 0, dry_mode = 0, no_chain = 0, blocks_per_cu = 0;   // KMC_SHADOW, KMC_DRYRUN, KMC_NO_CHAIN, KMC_BLOCKS_PER_CU (tuning_open)
+    uint32_t xflags = 0;                                             // KMC_XFLAGS
+    uint64_t chain_max = KMC_CHAIN_DEFAULT;                          // KMC_CHAIN_MAX
+    hipFunction_t f_expand_dry = nullptr;   // in a -DKMC_TUNING=1 build of the search's code object only
+    u64* table2 = nullptr;                  // the shadow pass's copy of the seen-set
+    double dry_seconds = 0;                 // dry / shadow passes of the current search
+    uint64_t prof_dry[8] = {0};
+};
+#endif
+
 struct kmc_handle {
     kmc_config cfg{};
     KmcLayout lay{};
@@ -69,12 +96,12 @@ struct kmc_handle {
     bool first_clear_timed = false;
     std::string cache_dir;                  // kmc_config.cache_dir, copied: the later code objects (ensure_mode) are looked up
                                             // long after kmc_open returned and the caller's string may be gone
-    std::string jit_defines;                // KMC_JIT_DEFINES as it stood when the handle was opened
-    int layout_mode = KMC_LAYOUT_AUTO;      // KMC_LAYOUT likewise (the later code objects are specialised for the same layout)
-    bool verify = false;                    // KMC_VERIFY likewise
+    kmc_knobs knobs;                        // the environment as it stood when the handle was opened
+#if KMC_TUNING
+    kmc_tuning tuning;
+#endif
     hipModule_t mod = nullptr;              // the search's code object: k_expand (LOCAL), k_inv, k_insert, k_init, k_find, k_packrow
     hipFunction_t f_expand = nullptr, f_inv = nullptr, f_insert = nullptr, f_init = nullptr, f_find = nullptr, f_packrow = nullptr;
-    hipFunction_t f_expand_dry = nullptr;   // only in a KMC_TUNING build of `mod` (KMC_DRYRUN / KMC_SHADOW tuning aids)
     hipModule_t mod_sh = nullptr, mod_en = nullptr;   // k_expand in SHARDED / ENUM mode: loaded when first needed (ensure_mode)
     hipFunction_t f_expand_sh = nullptr, f_expand_en = nullptr;
     hipModule_t mod_verify = nullptr;       // KMC_VERIFY=1: a second, differently compiled code object whose dry k_expand regenerates every level
@@ -83,15 +110,16 @@ struct kmc_handle {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_chain[2 * KMC_CHAIN] = {nullptr};  // chained launches: one pair per level of a batch
-    hipEvent_t ev_aux[2] = {nullptr, nullptr};       // around the clear of the seen-set (reset_run) and around k_inv
+    hipEvent_t ev_aux[2] = {nullptr, nullptr};       // around the clear of the seen-set (reset_run) and around k_inv: created by reset_run
     bool clear_pending = false;                      // ev_aux brackets a clear whose duration has not been read yet
     std::vector<kmc_level_stat> level_stats;         // one record per expansion of the last search (kmc_level_stats)
     double step_expand_ms = 0;                       // stepping: k_expand time of the level being built (kmc_step_finish books it)
     int rec_words = 0;  // exchange / insert record size: W, +1 when predecessor fingerprints are kept
     int n_cus = 256;
     int blocks_per_cu = 4;  // k_expand residency, from the occupancy query at open
-    u64 *table = nullptr, *pred = nullptr, *table2 = nullptr;
-    std::vector<std::pair<void*, size_t>> mapped;   // buffers that are mapped ranges of chunks, not hipMalloc's (seen_set_alloc): base, bytes
+    u64 *table = nullptr, *pred = nullptr;
+    struct mapped_range { void* base; size_t bytes, chunk; };
+    std::vector<mapped_range> mapped;   // buffers that are mapped ranges of chunks, not hipMalloc's (seen_set_alloc)
     u64* sent = nullptr;      // n_shards > 1: sender-side filter of fingerprints already shipped
     uint64_t sent_cap = 0;
     uint64_t table_cap = 0;      // slots
@@ -130,8 +158,7 @@ struct kmc_handle {
     uint64_t nfact = 1;
     int planes = 0;              // words per state in a frontier: W, and under symmetry one more — the order of the state's stabiliser
     double t_start = 0;
-    double dry_seconds = 0;
-    uint64_t prof[8] = {0}, prof_dry[8] = {0};
+    uint64_t prof[8] = {0};      // per-wave ticks of a -DKMC_PROFILE=1 build of the kernels (run_levels prints them)
     // per-level exchange under the ABI (n_shards > 1): RCCL communicator, receive area, count/statistics rows
     ncclComm_t comm = nullptr;
     u64* recv = nullptr;             // device: everything this shard receives in one level, contiguous
@@ -168,6 +195,10 @@ int64_t compiler_id_mine();
 int64_t compiler_id_pinned();
 bool validate(const kmc_config& c, KmcLayout* lay, std::string* name, std::string* inst, int layout_mode = -2);
 int layout_mode_from_env();   // KMC_LAYOUT as it stands now (-1: not a layout's name)
+// the environment: one call per read (a handle's: read_knobs; the others have no handle)
+inline const char* env_str(const char* name, const char* unset = nullptr) { const char* e = getenv(name); return e ? e : unset; }
+inline long long env_int(const char* name, long long unset) { const char* e = getenv(name); return e ? atoll(e) : unset; }
+inline bool env_flag(const char* name) { return env_int(name, 0) != 0; }
 int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<char>* code, std::string* kname,
                     const char* extra_options = nullptr, std::string* path_out = nullptr, unsigned mode = KMC_MODE_LOCAL,
                     const std::string* jit_defines = nullptr, int layout_mode = -2);
@@ -181,10 +212,6 @@ int ensure_mode(kmc_handle* h, unsigned mode);
 int launch_expand(kmc_handle* h, unsigned mode, const KmcArgs& a, unsigned grid, hipStream_t stream = nullptr, bool verify = false);
 int launch_inv(kmc_handle* h, const KmcArgs& a, uint64_t n);
 // the seen-set's memory: a range of addresses mapped from 8 MiB physical chunks (hipMalloc when that cannot be had) — see the definition
-#ifndef KMC_SEEN_SET_SPREAD_DEFAULT
-#define KMC_SEEN_SET_SPREAD_DEFAULT 1   // KMC_SEEN_SET_SPREAD: the seen-set's chunks lie over this many times their own size of the HBM
-                                        // (seen_set_alloc: spacers).  1 = as the chunks come: the spread costs seconds at open and close
-#endif
 u64* seen_set_alloc(kmc_handle* h, size_t bytes, bool chunks = true);
 void seen_set_free(kmc_handle* h, u64* p);
 KmcArgs base_args(kmc_handle* h, int ctl_slot);
@@ -199,6 +226,11 @@ int reset_run(kmc_handle* h);
 uint64_t weighted(const kmc_handle* h, uint64_t raw, uint64_t corr);
 uint64_t queue_now(const kmc_handle* h);
 void book_level(kmc_handle* h, uint64_t produced, const KmcLevelCtl& c);
+// the load at which a search ends with KMC_V_TABLE_FULL, before linear probing degenerates (sized for load <= 0.5, still fine at 0.9)
+constexpr double KMC_TABLE_LOAD_LIMIT = 0.92;
+// one expansion of kmc_run's loop (`c`: its control block) is folded into the result and the level it produced becomes the current
+// one; false when the search ends here (a verdict, nothing produced, the table past its load limit) or *rc is set
+bool advance_level(kmc_handle* h, const KmcLevelCtl& c, double expand_ms, int* rc);
 int check_conservation(kmc_handle* h, const KmcLevelCtl& c, uint64_t inserted);
 bool absorb(kmc_handle* h, const KmcLevelCtl& c, const u64* parent_frontier, const uint64_t* parent_seg, int* rc);
 int do_begin(kmc_handle* h);
@@ -211,6 +243,29 @@ void range_pop();
 
 // ---- kmc_engine_exchange.cpp ----
 void comm_release(kmc_handle* h);
+
+// ---- kmc_engine_tuning.cpp: what the product's code calls of the tuning aids; no-ops in libkmc.so ----
+#if KMC_TUNING
+void tuning_open(kmc_handle* h);                               // at kmc_open: the aids' environment, the dry kernel if `mod` holds one
+void tuning_close(kmc_handle* h);
+hipFunction_t tuning_dry_kernel(const kmc_handle* h);
+bool tuning_unchained(const kmc_handle* h);                    // an aid that runs level by level is on
+int tuning_shadow_level(kmc_handle* h, const KmcArgs& a);      // before a level's launch
+int tuning_dry_level(kmc_handle* h, const KmcArgs& a);         // after it
+void tuning_report(kmc_handle* h);                             // at the end of a search
+int tuning_blocks_per_cu(const kmc_handle* h);                 // 0: the handle's own
+uint64_t tuning_chain_max(const kmc_handle* h);
+#else
+static inline void tuning_open(kmc_handle*) {}
+static inline void tuning_close(kmc_handle*) {}
+static inline hipFunction_t tuning_dry_kernel(const kmc_handle*) { return nullptr; }
+static inline bool tuning_unchained(const kmc_handle*) { return false; }
+static inline int tuning_shadow_level(kmc_handle*, const KmcArgs&) { return KMC_OK; }
+static inline int tuning_dry_level(kmc_handle*, const KmcArgs&) { return KMC_OK; }
+static inline void tuning_report(kmc_handle*) {}
+static inline int tuning_blocks_per_cu(const kmc_handle*) { return 0; }
+static inline uint64_t tuning_chain_max(const kmc_handle*) { return KMC_CHAIN_DEFAULT; }
+#endif
 
 }  // namespace kmc_engine
 

@@ -45,7 +45,7 @@ int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode) {
     if (mode < -1 || mode > (int32_t)KMC_MODE_ENUM) return fail(KMC_E_ARG, "mode %d: expected -1 (all), 0 (search), 1 (sharded), 2 (enum)", mode);
     std::vector<char> code;
     std::string kname;
-    const bool verify = getenv("KMC_VERIFY") && atoi(getenv("KMC_VERIFY"));
+    const bool verify = env_flag("KMC_VERIFY");
     for (unsigned m = 0; m <= KMC_MODE_ENUM; ++m) {
         if (mode >= 0 && (unsigned)mode != m) continue;
         int rc = get_code_object(*cfg, arch ? arch : "gfx950", &code, &kname, verify ? KMC_VERIFY_PRIMARY_OPTIONS : nullptr, nullptr, m);
@@ -83,7 +83,7 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     seen_set_free(h, h->table);
     if (!h->paired) seen_set_free(h, h->pred);   // (paired: the predecessors are the slots' second words)
-    if (h->table2) (void)hipFree(h->table2);
+    tuning_close(h);
     seen_set_free(h, h->sent);
     if (h->frontier[0]) (void)hipFree(h->frontier[0]);
     if (h->frontier[1]) (void)hipFree(h->frontier[1]);
@@ -109,6 +109,8 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     for (hipEvent_t e : h->ev_chain)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_aux)
+        if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->mod_verify) (void)hipModuleUnload(h->mod_verify);
     if (h->mod_sh) (void)hipModuleUnload(h->mod_sh);
@@ -119,8 +121,22 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
 
 }  // extern "C"
 
+// The one place a handle asks the environment: everything it may change about a handle, as it stands when the handle is opened.
+static void read_knobs(kmc_knobs* k) {
+    k->verbose = env_str("KMC_VERBOSE") != nullptr;
+    k->verify = env_flag("KMC_VERIFY");
+    k->jit_defines = env_str("KMC_JIT_DEFINES", "");
+    k->layout_mode = layout_mode_from_env();
+    k->paired_slots = (int)env_int("KMC_PAIRED_SLOTS", 1);
+    k->send_filter = env_str("KMC_SEND_FILTER") ? (int)env_flag("KMC_SEND_FILTER") : -1;
+    const int spread = (int)env_int("KMC_SEEN_SET_SPREAD", 1);
+    k->seen_set_spread = spread < 1 ? 1 : spread > 64 ? 64 : spread;
+    k->seen_set_chunk_log2 = (int)env_int("KMC_SEEN_SET_CHUNK_LOG2", 23);
+}
+
 static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     h->cfg = *cfg;
+    read_knobs(&h->knobs);
     if (cfg->cache_dir) {
         h->cache_dir = cfg->cache_dir;
         h->cfg.cache_dir = h->cache_dir.c_str();
@@ -129,8 +145,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     if (h->cfg.n_shards > KMC_MAX_SHARDS || h->cfg.shard_id < 0 || h->cfg.shard_id >= h->cfg.n_shards)
         return fail(KMC_E_ARG, "bad shard configuration %d/%d", h->cfg.shard_id, h->cfg.n_shards);
     std::string name, inst;
-    h->layout_mode = layout_mode_from_env();   // read once: the handle's later code objects follow it (ensure_mode)
-    if (!validate(h->cfg, &h->lay, &name, &inst, h->layout_mode)) {
+    if (!validate(h->cfg, &h->lay, &name, &inst, h->knobs.layout_mode)) {
         std::vector<char> dummy;
         return get_code_object(h->cfg, "gfx950", &dummy, &name);  // produces the KMC_E_ARG message
     }
@@ -159,18 +174,13 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     h->arch = arch;
 
     std::vector<char> code;
-    const bool verify = getenv("KMC_VERIFY") && atoi(getenv("KMC_VERIFY"));
-    h->verify = verify;
-    h->jit_defines = getenv("KMC_JIT_DEFINES") ? getenv("KMC_JIT_DEFINES") : "";
+    const bool verify = h->knobs.verify;
     int rc = get_code_object(h->cfg, arch, &code, &h->kname, verify ? KMC_VERIFY_PRIMARY_OPTIONS : nullptr, nullptr, KMC_MODE_LOCAL,
-                             &h->jit_defines, h->layout_mode);
+                             &h->knobs.jit_defines, h->knobs.layout_mode);
     if (rc) return rc;
     HIP_TRY(hipModuleLoadData(&h->mod, code.data()));
     HIP_TRY(hipModuleGetFunction(&h->f_expand, h->mod, ("kmc_expand_" + h->kname).c_str()));
-    if (hipModuleGetFunction(&h->f_expand_dry, h->mod, ("kmc_expand_dry_" + h->kname).c_str()) != hipSuccess) {
-        h->f_expand_dry = nullptr;   // (not a tuning build)
-        (void)hipGetLastError();
-    }
+    tuning_open(h);
     HIP_TRY(hipModuleGetFunction(&h->f_inv, h->mod, ("kmc_inv_" + h->kname).c_str()));
     HIP_TRY(hipModuleGetFunction(&h->f_insert, h->mod, ("kmc_insert_" + h->kname).c_str()));
     HIP_TRY(hipModuleGetFunction(&h->f_init, h->mod, ("kmc_init_" + h->kname).c_str()));
@@ -184,7 +194,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
         // the checksum of the successors' fingerprints of the two builds must agree.
         std::vector<char> vcode;
         std::string vname;
-        rc = get_code_object(h->cfg, arch, &vcode, &vname, KMC_VERIFY_OPTIONS, nullptr, KMC_MODE_LOCAL, &h->jit_defines, h->layout_mode);
+        rc = get_code_object(h->cfg, arch, &vcode, &vname, KMC_VERIFY_OPTIONS, nullptr, KMC_MODE_LOCAL, &h->knobs.jit_defines, h->knobs.layout_mode);
         if (rc) return rc;
         HIP_TRY(hipModuleLoadData(&h->mod_verify, vcode.data()));
         HIP_TRY(hipModuleGetFunction(&h->f_expand_verify, h->mod_verify, ("kmc_expand_dry_" + vname).c_str()));
@@ -218,8 +228,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     // issues a batch's first probe one flush early (kmc_kernels.h: DEFER), the paired slots take the undeferred walk, and at seven
     // brokers that costs more than the second line (config 5, ten levels: 26.9 ms separate, 27.6 paired).  KMC_PAIRED_SLOTS=0
     // restores the separate table everywhere (A/B), =2 forces the slots on wide states too; 128-bit entries keep it (their slot is full).
-    static const int paired_env = getenv("KMC_PAIRED_SLOTS") ? atoi(getenv("KMC_PAIRED_SLOTS")) : 1;
-    const bool paired_ok = paired_env == 2 || (paired_env == 1 && h->W < KMC_DEFER_MIN_WORDS);
+    const bool paired_ok = h->knobs.paired_slots == 2 || (h->knobs.paired_slots == 1 && h->W < KMC_DEFER_MIN_WORDS);
     h->paired = cfg->keep_trace && !cfg->wide_fingerprint && paired_ok;
     const uint64_t slot_bytes = 8 * h->slot_words + (cfg->keep_trace ? 8 : 0);
     // auto-sizing: half of the budget for the table; a shard also keeps a sender-side filter of twice the table
@@ -243,7 +252,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     h->fcap = fcap;
     h->seg_cap = fcap / KMC_SEGS;
     if (!(h->table = seen_set_alloc(h, tcap * h->stride_words() * 8))) return fail(KMC_E_NOMEM, "cannot allocate %llu table slots", (unsigned long long)tcap);
-    if (getenv("KMC_VERBOSE"))
+    if (h->knobs.verbose)
         fprintf(stderr, "[kmc] seen-set: %llu slots x %llu B at %p (%s)\n", (unsigned long long)tcap, (unsigned long long)(h->stride_words() * 8), (void*)h->table,
                 h->mapped.empty() ? "one hipMalloc" : "mapped from chunks");
     if (h->paired) h->pred = h->table + 1;
@@ -262,8 +271,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     // is on where the wire is the bottleneck (P <= 4: one to three xGMI links per GPU carry everything) and off beyond
     // (profiles/r02_loopback_filter.jsonl: k_expand per shard 11.6 -> 8.1 ms at P = 8).  KMC_SEND_FILTER=1 / 0 forces it.
     bool want_filter = h->cfg.n_shards > 1 && h->cfg.n_shards <= 4;
-    if (const char* e = getenv("KMC_SEND_FILTER")) want_filter = h->cfg.n_shards > 1 && atoi(e) != 0;
-    if (getenv("KMC_NO_SEND_FILTER") && atoi(getenv("KMC_NO_SEND_FILTER"))) want_filter = false;
+    if (h->knobs.send_filter >= 0) want_filter = h->cfg.n_shards > 1 && h->knobs.send_filter != 0;
     // 128-bit entries: the sender-side filter remembers 64-bit fingerprints only — a second distinct remote state with the
     // same fingerprint would be dropped at the sender and never meet the owner's check-word comparison, and the conservation
     // law (probed is counted before the filter) could not see it.  No filter then, whatever the environment asks for.

@@ -12,35 +12,6 @@ int kmc_run(kmc_handle* h, kmc_progress_cb cb, void* user) {
     if (h->cfg.n_shards != 1) return fail(KMC_E_STATE, "kmc_run drives one GPU; use the kmc_step_* interface for shards");
     HIP_TRY(hipSetDevice(h->cfg.device));
     h->stepping = false;
-    if (const char* which = getenv("KMC_DEBUG_REALLOC")) {
-        // tuning aid (profiles/r06_table_size_and_placement.txt, item 3): ONE of the handle's buffers — table | f0 | f1 | ctl — is
-        // moved to another place in the HBM before this search; k_expand's time follows where the seen-set lies
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        auto move = [&](u64*& p, size_t bytes) -> int {
-            u64* q = nullptr;
-            void* pad = nullptr;
-            (void)hipMalloc(&pad, 768ull << 20);   // (leaked: shifts where the next buffers land)
-            if (hipMalloc(&q, bytes) != hipSuccess) return fail(KMC_E_NOMEM, "debug realloc");
-            HIP_TRY(hipMemcpy(q, p, bytes, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipFree(p));
-            p = q;
-            return KMC_OK;
-        };
-        int rc0 = KMC_OK;
-        if (!strcmp(which, "table")) {   // (through the seen-set's own allocator: chunks, or one hipMalloc under KMC_SEEN_SET_CHUNK_LOG2=0)
-            void* pad = nullptr;
-            (void)hipMalloc(&pad, 768ull << 20);
-            u64* q = seen_set_alloc(h, h->table_cap * h->stride_words() * 8);
-            if (!q) return fail(KMC_E_NOMEM, "debug realloc");
-            seen_set_free(h, h->table);
-            h->table = q;
-            if (h->paired) h->pred = q + 1;
-        }
-        else if (!strcmp(which, "f0")) rc0 = move(h->frontier[0], h->fcap * 8ull * h->planes);
-        else if (!strcmp(which, "f1")) rc0 = move(h->frontier[1], h->fcap * 8ull * h->planes);
-        else if (!strcmp(which, "ctl")) { u64* c = (u64*)h->ctl; rc0 = move(c, KMC_CTL_SLOTS * sizeof(KmcLevelCtl)); h->ctl = (KmcLevelCtl*)c; }
-        if (rc0) return rc0;
-    }
     int rc = do_begin(h);
     if (rc) return rc;
     return run_levels(h, cb, user, true);
@@ -61,6 +32,39 @@ int kmc_resume(kmc_handle* h, kmc_progress_cb cb, void* user) {
 
 }  // extern "C"
 
+// KMC_VERIFY: the second build regenerates the level that `a` launched and `c` reports; the counts must agree
+static int verify_level(kmc_handle* h, const KmcArgs& a, const KmcLevelCtl& c) {
+    int rc = KMC_OK;
+    KmcArgs v = a;
+    v.ctl = h->ctl + 2;
+    if ((rc = zero_ctl(h, 2))) return rc;
+    if ((rc = launch_expand(h, KMC_MODE_DRY, v, expand_grid(h, h->n_cur), nullptr, true))) return rc;
+    KmcLevelCtl vc;
+    HIP_TRY(hipMemcpyAsync(&vc, h->ctl + 2, KMC_CTL_LOCAL_BYTES, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    bool same = vc.deadlock_count == c.deadlock_count;
+    for (int k = 0; k < KMC_MAX_KINDS; ++k) same = same && vc.generated[k] == c.generated[k];
+    for (int k = 0; k < 4; ++k) same = same && vc.viol_count[k] == c.viol_count[k];
+    // (orbit counting: the deficits taken when a state is expanded — the second build finds the stabilisers again)
+    for (int k = 0; k < KMC_MAX_KINDS; ++k) same = same && vc.corr_gen[k] == c.corr_gen[k];
+    for (int k = 0; k < 4; ++k) same = same && vc.corr_viol[k] == c.corr_viol[k];
+    same = same && vc.corr_dead == c.corr_dead && vc.corr_repeats == c.corr_repeats;
+    // ... and the successors themselves: how many reached the sink, and the order-independent checksum of their
+    // fingerprints (taken where a successor enters the sink — behind the ring and the flush, where round 1's
+    // miscompiled kernel lost some while every count above still agreed)
+    const bool same_succ = vc.probed == c.probed && vc.fp_sum == c.fp_sum && vc.fp_xor == c.fp_xor &&
+                           vc.repeats == c.repeats && vc.outside == c.outside;
+    if (!same || !same_succ) {
+        h->res.verdict = KMC_V_ERROR;
+        return fail(KMC_E_DEVICE, "KMC_VERIFY: the two builds of kmc_expand_%s disagree at level %llu (%s): one of them "
+                                  "is miscompiled", h->kname.c_str(), (unsigned long long)h->level,
+                    same ? "the successors reaching the seen-set differ: count or fingerprint checksum"
+                         : "generated / deadlock / violation counts differ");
+    }
+    h->verify_levels++;
+    return KMC_OK;
+}
+
 static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh) {
     int rc = KMC_OK;
     kmc_result& r = h->res;
@@ -75,9 +79,8 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
         cb(&info, user);
     };
     if (fresh) report();
-    bool stop = false;
     const uint64_t max_levels = h->cfg.max_levels ? h->cfg.max_levels : ~0ull;
-    while (!stop && h->n_cur > 0) {
+    while (h->n_cur > 0) {
         if (h->level >= max_levels) {
             // the last frontier is not expanded: give its states their invariant check now
             if ((rc = zero_ctl(h, 2))) return rc;
@@ -108,14 +111,11 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
             r.queue_left = queue_now(h);
             break;
         }
-        static const int shadow = getenv("KMC_SHADOW") ? atoi(getenv("KMC_SHADOW")) : 0;
-        static const int dry_mode = getenv("KMC_DRYRUN") ? atoi(getenv("KMC_DRYRUN")) : 0;
-        static const int no_chain = getenv("KMC_NO_CHAIN") ? atoi(getenv("KMC_NO_CHAIN")) : 0;
         // Under -continue a violation does not end the search, so levels queued behind the violating one would run and
         // overwrite its parent frontier before the host could fetch the witness (find_state / find_outside_witness):
         // such runs go level by level until the first violation has been recorded, and chain from there on.
         const bool witness_pending = h->cfg.continue_on_violation && h->cfg.invariant_mask && r.violated_invariant < 0;
-        if (!cb && !shadow && !dry_mode && !no_chain && !h->f_expand_verify && !witness_pending) {
+        if (!cb && !tuning_unchained(h) && !h->f_expand_verify && !witness_pending) {
             // ---- chained launches -------------------------------------------------------------------------
             // Nobody watches the levels go by, so up to KMC_CHAIN of them are queued back to back and the host
             // waits ONCE: a level launched behind another one takes its segment sizes from that level's control
@@ -123,16 +123,16 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
             // this leaves a launch and two event records on the host instead of memset + launch + copy + wait
             // (46 levels, 7 of them under 1024 states: 2.4 ms of a 38 ms check in round 1).
             uint64_t B = max_levels - h->level;
-            static const uint64_t chain_max = getenv("KMC_CHAIN_MAX") ? (uint64_t)atoi(getenv("KMC_CHAIN_MAX")) : 16;
+            const uint64_t chain_max = tuning_chain_max(h);
             if (B > KMC_CHAIN) B = KMC_CHAIN;
             if (chain_max >= 1 && B > chain_max) B = chain_max;
             const uint64_t fan = max_fanout(h) ? max_fanout(h) : 1;
             {
-                // The load limit of the table (0.92, below) is a HOST decision, taken after a level: a batch is therefore
+                // The load limit of the table (KMC_TABLE_LOAD_LIMIT) is a HOST decision, taken after a level: a batch is therefore
                 // only as long as its levels provably stay under it — each level adds at most min(fan x its input,
                 // frontier capacity) states.  (Without this a batch could run the table far past the limit before the
                 // host looked, and after such a stop h->cur / seg_n no longer described the device's frontier: ADVICE r2.)
-                const double room = 0.92 * (double)h->table_cap - (double)r.orbit_representatives;
+                const double room = KMC_TABLE_LOAD_LIMIT * (double)h->table_cap - (double)r.orbit_representatives;
                 uint64_t in = h->n_cur, fit = 0;
                 double sum = 0;
                 for (; fit < B; ++fit) {
@@ -180,64 +180,23 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
                 r.expand_launches++;
                 chain_ms[i] = ms;
             }
-            bool done = false;
-            for (uint64_t i = 0; i < B && !done; ++i) {
+            bool go = true;
+            for (uint64_t i = 0; i < B && go; ++i) {
                 const KmcLevelCtl c = h->ctl_host[i];
                 if (c.halt) break;   // the device ended the chain here; the host decides below whether the search goes on
                 for (int k = 0; k < 8; ++k) h->prof[k] += c.prof[k];
-                uint64_t new_seg[KMC_SEGS];
-                const uint64_t produced = produced_segments(h, c, new_seg);
-                stop = absorb(h, c, h->frontier[h->cur], h->seg_n, &rc);
+                go = advance_level(h, c, chain_ms[i], &rc);
                 if (rc) return rc;
-                if (stop) {
-                    r.queue_left = queue_now(h);
-                    done = true;
-                    break;
-                }
-                note_level(h, c, h->n_cur, produced, chain_ms[i]);
-                if (produced == 0) {
-                    h->n_cur = 0;
-                    done = true;
-                    break;
-                }
-                h->cur ^= 1;
-                h->n_cur = produced;
-                for (int sg = 0; sg < KMC_SEGS; ++sg) h->seg_n[sg] = new_seg[sg];
-                h->level++;
-                r.depth = h->level;
-                book_level(h, produced, c);
-                if ((double)r.orbit_representatives > 0.92 * (double)h->table_cap && r.verdict == KMC_V_OK) {
-                    r.verdict = KMC_V_TABLE_FULL;
-                    r.queue_left = queue_now(h);
-                    stop = done = true;
-                }
             }
-            if (done) break;
+            if (!go) break;
             continue;
         }
         const int slot = (int)(h->level & 1);
-        const int nxt = h->cur ^ 1;
         if ((rc = zero_ctl(h, slot))) return rc;
         KmcArgs a = base_args(h, slot);
         a.fin = h->frontier[h->cur];
-        a.fout = h->frontier[nxt];
-        if (shadow) {  // tuning aid: the identical level first runs on a copy of the table, with KMC_XFLAGS applied
-            if (!h->table2) HIP_TRY(hipMalloc(&h->table2, h->table_cap * h->stride_words() * 8));
-            HIP_TRY(hipMemcpyAsync(h->table2, h->table, h->table_cap * h->stride_words() * 8, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(hipMemsetAsync(h->ctl + 2, 0, sizeof(KmcLevelCtl), h->stream));
-            KmcArgs x = a;
-            x.table = h->table2;
-            if (h->paired) x.pred = h->table2 + 1;
-            x.ctl = h->ctl + 2;
-            x.flags |= getenv("KMC_XFLAGS") ? (uint32_t)atoi(getenv("KMC_XFLAGS")) : 0u;
-            HIP_TRY(hipEventRecord(h->ev0, h->stream));
-            if ((rc = launch_expand(h, KMC_MODE_LOCAL, x, expand_grid(h, h->n_cur)))) return rc;
-            HIP_TRY(hipEventRecord(h->ev1, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            float xms = 0;
-            HIP_TRY(hipEventElapsedTime(&xms, h->ev0, h->ev1));
-            h->dry_seconds += 1e-3 * xms;
-        }
+        a.fout = h->frontier[h->cur ^ 1];
+        if ((rc = tuning_shadow_level(h, a))) return rc;
         range_push("kmc %s: level %llu (%llu states)", h->kname.c_str(), (unsigned long long)h->level, (unsigned long long)h->n_cur);
         HIP_TRY(hipEventRecord(h->ev0, h->stream));
         if ((rc = launch_expand(h, KMC_MODE_LOCAL, a, expand_grid(h, h->n_cur)))) return rc;
@@ -250,81 +209,13 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
         r.expand_launches++;
         const KmcLevelCtl c = *h->ctl_host;
         for (int k = 0; k < 8; ++k) h->prof[k] += c.prof[k];
-        if (h->f_expand_verify) {  // KMC_VERIFY: the second build regenerates this level; the counts must agree
-            KmcArgs v = a;
-            v.ctl = h->ctl + 2;
-            if ((rc = zero_ctl(h, 2))) return rc;
-            if ((rc = launch_expand(h, KMC_MODE_DRY, v, expand_grid(h, h->n_cur), nullptr, true))) return rc;
-            KmcLevelCtl vc;
-            HIP_TRY(hipMemcpyAsync(&vc, h->ctl + 2, KMC_CTL_LOCAL_BYTES, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            bool same = vc.deadlock_count == c.deadlock_count;
-            for (int k = 0; k < KMC_MAX_KINDS; ++k) same = same && vc.generated[k] == c.generated[k];
-            for (int k = 0; k < 4; ++k) same = same && vc.viol_count[k] == c.viol_count[k];
-            // (orbit counting: the deficits taken when a state is expanded — the second build finds the stabilisers again)
-            for (int k = 0; k < KMC_MAX_KINDS; ++k) same = same && vc.corr_gen[k] == c.corr_gen[k];
-            for (int k = 0; k < 4; ++k) same = same && vc.corr_viol[k] == c.corr_viol[k];
-            same = same && vc.corr_dead == c.corr_dead && vc.corr_repeats == c.corr_repeats;
-            // ... and the successors themselves: how many reached the sink, and the order-independent checksum of their
-            // fingerprints (taken where a successor enters the sink — behind the ring and the flush, where round 1's
-            // miscompiled kernel lost some while every count above still agreed)
-            const bool same_succ = vc.probed == c.probed && vc.fp_sum == c.fp_sum && vc.fp_xor == c.fp_xor &&
-                                   vc.repeats == c.repeats && vc.outside == c.outside;
-            if (!same || !same_succ) {
-                r.verdict = KMC_V_ERROR;
-                return fail(KMC_E_DEVICE, "KMC_VERIFY: the two builds of kmc_expand_%s disagree at level %llu (%s): one of them "
-                                          "is miscompiled", h->kname.c_str(), (unsigned long long)h->level,
-                            same ? "the successors reaching the seen-set differ: count or fingerprint checksum"
-                                 : "generated / deadlock / violation counts differ");
-            }
-            h->verify_levels++;
-        }
-        const int dry = dry_mode;
-        if (dry) {  // tuning aid: time the same level again without table writes / frontier traffic
-            KmcArgs d = a;  // 1: no table access at all, 2: + read-only probes, 3: + invariants on every successor
-            if (dry >= 2) d.flags |= KMC_FLAG_DRY_PROBE;
-            if (dry == 3) d.flags |= KMC_FLAG_DRY_INV;
-            if (dry == 4) d.flags |= KMC_FLAG_DRY_ATOM;
-            if (dry == 5) d.flags |= KMC_FLAG_DRY_RAND;
-            d.ctl = h->ctl + 2;
-            HIP_TRY(hipEventRecord(h->ev0, h->stream));
-            if ((rc = launch_expand(h, KMC_MODE_DRY, d, expand_grid(h, h->n_cur)))) return rc;
-            HIP_TRY(hipEventRecord(h->ev1, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            float dms = 0;
-            HIP_TRY(hipEventElapsedTime(&dms, h->ev0, h->ev1));
-            h->dry_seconds += 1e-3 * dms;
-            KmcLevelCtl dc;
-            HIP_TRY(hipMemcpy(&dc, h->ctl + 2, sizeof dc, hipMemcpyDeviceToHost));
-            for (int k = 0; k < 8; ++k) h->prof_dry[k] += dc.prof[k];
-            HIP_TRY(hipMemsetAsync(h->ctl + 2, 0, sizeof(KmcLevelCtl), h->stream));
-        }
-        uint64_t new_seg[KMC_SEGS];
-        const uint64_t produced = produced_segments(h, c, new_seg);
-        stop = absorb(h, c, h->frontier[h->cur], h->seg_n, &rc);
+        if (h->f_expand_verify && (rc = verify_level(h, a, c))) return rc;
+        if ((rc = tuning_dry_level(h, a))) return rc;
+        const uint64_t expanded = h->level;
+        const bool go = advance_level(h, c, (double)ms, &rc);
         if (rc) return rc;
-        if (stop) {  // invariant (produced level rolled back), deadlock, table/frontier full
-            r.queue_left = queue_now(h);
-            break;
-        }
-        note_level(h, c, h->n_cur, produced, (double)ms);
-        if (produced == 0) {
-            h->n_cur = 0;
-            break;
-        }
-        h->cur = nxt;
-        h->n_cur = produced;
-        for (int sg = 0; sg < KMC_SEGS; ++sg) h->seg_n[sg] = new_seg[sg];
-        h->level++;
-        r.depth = h->level;
-        book_level(h, produced, c);
-        report();
-        // stop before linear probing degenerates (sized for load <= 0.5, still fine at 0.9)
-        if ((double)r.orbit_representatives > 0.92 * (double)h->table_cap && r.verdict == KMC_V_OK) {
-            r.verdict = KMC_V_TABLE_FULL;
-            r.queue_left = queue_now(h);
-            break;
-        }
+        if (h->level != expanded) report();   // (a level entered the books)
+        if (!go) break;
     }
     r.n_levels = h->levels.size();
     r.seconds_total = now_s() - h->t_start;
@@ -339,19 +230,7 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
                     (double)h->prof[5] / (double)h->prof[6], (unsigned long long)h->prof[6]);
         for (int k = 0; k < 8; ++k) h->prof[k] = 0;
     }
-    if (h->prof_dry[7]) {
-        const double tot = (double)h->prof_dry[7];
-        fprintf(stderr, "[kmc] DRY per-wave ticks: load+extract+inv %.1f%%  guards %.1f%%  effects+push(incl flush) %.1f%%  "
-                        "of which flush %.1f%%  tail %.1f%%  (total %.3g ticks)\n",
-                100 * h->prof_dry[0] / tot, 100 * h->prof_dry[1] / tot, 100 * h->prof_dry[2] / tot,
-                100 * h->prof_dry[3] / tot, 100 * h->prof_dry[4] / tot, tot);
-        for (int k = 0; k < 8; ++k) h->prof_dry[k] = 0;
-    }
-    if (h->dry_seconds > 0) {
-        fprintf(stderr, "[kmc] dry/shadow expand: %.3f ms vs real %.3f ms\n",
-                1e3 * h->dry_seconds, 1e3 * r.seconds_expand);
-        h->dry_seconds = 0;
-    }
+    tuning_report(h);
     return KMC_OK;
 }
 
@@ -403,23 +282,34 @@ int kmc_frontier_states(kmc_handle* h, uint64_t* words, uint64_t cap_states, uin
     return KMC_OK;
 }
 
-int kmc_successors(kmc_handle* h, const uint64_t* words, uint64_t* out, uint64_t cap, uint64_t* n_out) {
-    if (!h || !words || !n_out) return fail(KMC_E_ARG, "null argument");
-    if (!h->table) return fail(KMC_E_STATE, "host-only handle");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    // the auxiliary frontier is the scratch buffer viewed as SoA with stride 1... planes must be
-    // fin[k*stride + 0], so stride 1 puts the W words back to back
+}  // extern "C"
+
+// One packed state becomes a frontier of its own, described by `a` (control slot 2, zeroed): the auxiliary frontier is the
+// scratch buffer viewed as SoA with stride 1 — planes must be fin[k*stride + 0], so stride 1 puts the W words back to back.
+static int stage_one_state(kmc_handle* h, const uint64_t* words, KmcArgs* a) {
     HIP_TRY(hipMemcpyAsync(h->scratch, words, h->W * 8, hipMemcpyHostToDevice, h->stream));
-    if (h->cfg.symmetry) {   // plane W of this one-state frontier: the stabiliser's order (no count is taken from an ENUM pass)
+    if (h->cfg.symmetry) {   // plane W of this one-state frontier: the stabiliser's order (no count is taken from such a pass)
         static const uint64_t one = 1;
         HIP_TRY(hipMemcpyAsync(h->scratch + h->W, &one, 8, hipMemcpyHostToDevice, h->stream));
     }
     int rc = zero_ctl(h, 2);
     if (rc) return rc;
-    KmcArgs a = base_args(h, 2);
-    a.fin = h->scratch;
-    a.fin_stride = 1;
-    for (int sg = 0; sg < KMC_SEGS; ++sg) a.seg_count[sg] = sg == 0 ? 1 : 0;
+    *a = base_args(h, 2);
+    a->fin = h->scratch;
+    a->fin_stride = 1;
+    for (int sg = 0; sg < KMC_SEGS; ++sg) a->seg_count[sg] = sg == 0 ? 1 : 0;
+    return KMC_OK;
+}
+
+extern "C" {
+
+int kmc_successors(kmc_handle* h, const uint64_t* words, uint64_t* out, uint64_t cap, uint64_t* n_out) {
+    if (!h || !words || !n_out) return fail(KMC_E_ARG, "null argument");
+    if (!h->table) return fail(KMC_E_STATE, "host-only handle");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    KmcArgs a;
+    int rc = stage_one_state(h, words, &a);
+    if (rc) return rc;
     a.send = h->enum_out;
     a.send_cap = h->enum_cap;
     a.inv_mask = 0;
@@ -452,17 +342,9 @@ int kmc_check_states(kmc_handle* h, const uint64_t* words, uint64_t n, uint32_t 
     if (!h->table) return fail(KMC_E_STATE, "host-only handle");
     HIP_TRY(hipSetDevice(h->cfg.device));
     for (uint64_t i = 0; i < n; ++i) {
-        HIP_TRY(hipMemcpyAsync(h->scratch, words + i * h->W, h->W * 8, hipMemcpyHostToDevice, h->stream));
-        if (h->cfg.symmetry) {
-            static const uint64_t one = 1;
-            HIP_TRY(hipMemcpyAsync(h->scratch + h->W, &one, 8, hipMemcpyHostToDevice, h->stream));
-        }
-        int rc = zero_ctl(h, 2);
+        KmcArgs a;
+        int rc = stage_one_state(h, words + i * h->W, &a);
         if (rc) return rc;
-        KmcArgs a = base_args(h, 2);
-        a.fin = h->scratch;
-        a.fin_stride = 1;
-        for (int sg = 0; sg < KMC_SEGS; ++sg) a.seg_count[sg] = sg == 0 ? 1 : 0;
         a.inv_mask = mask & 15u;
         if ((rc = launch_inv(h, a, 1))) return rc;
         if ((rc = read_ctl(h, 2))) return rc;

@@ -23,13 +23,55 @@ def header_functions():
     return sorted(set(re.findall(r"\b(kmc_[a-z_0-9]+)\s*\(", text)) - {"kmc_progress_cb"})
 
 
+TUNING_LIB = os.path.join(os.path.dirname(nat.LIB_PATH), "libkmc_tuning.so")   # the same engine + the tuning aids (csrc/Makefile)
+CSRC = os.path.join(ROOT, "kafka_specification_amd", "csrc")
+
+
 def test_library_exports_every_declared_symbol():
-    lib = C.CDLL(nat.LIB_PATH)
     names = header_functions()
     assert len(names) >= 25
-    for n in names:
-        assert hasattr(lib, n), f"libkmc.so does not export {n}"
+    for path in (nat.LIB_PATH, TUNING_LIB):
+        lib = C.CDLL(path)
+        for n in names:
+            assert hasattr(lib, n), f"{os.path.basename(path)} does not export {n}"
     assert sorted(n for n, _, _ in nat.SYMBOLS) == names  # the binding covers exactly the header
+
+
+def test_the_tuning_aids_are_in_the_tuning_library_only():
+    """The dry / shadow passes (their report line) live in libkmc_tuning.so and not in libkmc.so, and the buffer-moving
+    experiment that leaked device memory on purpose is in neither.  (Neither string occurs in the device source both embed.)"""
+    shipped, tuning = open(nat.LIB_PATH, "rb").read(), open(TUNING_LIB, "rb").read()
+    assert b"dry/shadow expand" not in shipped and b"dry/shadow expand" in tuning
+    assert b"KMC_DEBUG_REALLOC" not in shipped and b"KMC_DEBUG_REALLOC" not in tuning
+
+
+def _readme_table_names(heading):
+    """The KMC_* names that open a first-column cell of the table under `heading` of README.md."""
+    text = open(os.path.join(ROOT, "README.md")).read()
+    assert text.count("\n### " + heading) == 1, heading
+    section = text.split("\n### " + heading, 1)[1].split("\n#", 1)[0]
+    rows = [l for l in section.splitlines() if l.startswith("| `")]
+    return {m for l in rows for m in re.findall(r"`(KMC_[A-Z0-9_]+)", l.split(" | ")[0])}
+
+
+def test_the_environment_the_engine_reads_is_the_environment_the_readme_names():
+    """Every KMC_* variable handed to getenv / the env_* helpers (csrc/kmc_engine_internal.h) by the units of libkmc.so is a row
+    of README's "Environment the library honours", and the other way round; the same for kmc_engine_tuning.cpp and the "Tuning
+    build" table; and no unit keeps a value of the environment in a function-local static, where a handle opened later would
+    not see it change."""
+    import glob
+    read = re.compile(r'\b(?:getenv|env_str|env_int|env_flag)\(\s*"(KMC_[A-Z0-9_]+)"')
+    units = sorted(glob.glob(os.path.join(CSRC, "kmc_engine_*.cpp")))
+    assert len(units) == 7
+    shipped, tuning = set(), set()
+    for path in units:
+        text = open(path).read()
+        (tuning if path.endswith("kmc_engine_tuning.cpp") else shipped).update(read.findall(text))
+        assert not [l for l in text.splitlines() if "static const" in l and "getenv" in l], path
+        assert "getenv" not in text, path           # (the helpers are the only callers: kmc_engine_internal.h)
+    assert shipped == _readme_table_names("Environment the library honours") and len(shipped) == 12, sorted(shipped)
+    assert tuning == _readme_table_names("Tuning build") and len(tuning) == 6, sorted(tuning)
+    assert not shipped & tuning
 
 
 def test_struct_sizes_match_header_layout():

@@ -1,7 +1,8 @@
 """Where the seen-set's memory comes from (round 6, csrc/kmc_engine_core.cpp: seen_set_alloc): a range of addresses mapped from
 8 MiB physical chunks by default, one hipMalloc under KMC_SEEN_SET_CHUNK_LOG2=0 and whenever the mapping cannot be had.  The
-chunk size is read once per process, so every variant is its own process (the native front end, which says under KMC_VERBOSE
-which of the two it got); the answers must be the oracle's whichever memory the table lies in — with and without traces (the
+chunk size, the spread and the paired slots are a handle's knobs, read when it is opened (two handles of one process under two
+values: tests/test_gpu_knobs_and_tuning_build.py); here every variant is a run of the native front end, which says under
+KMC_VERBOSE which of the two it got; the answers must be the oracle's whichever memory the table lies in — with and without traces (the
 predecessor table goes through the same allocator), at a capacity that is not a multiple of the chunk, and after a handle that
 was closed and opened again in one process (the ranges are unmapped and released with the handle).
 """
@@ -142,7 +143,7 @@ def test_a_spread_seen_set_gives_the_same_search(spread, extra):
 
 def test_the_spacers_of_a_spread_seen_set_go_back_at_open():
     """A handle opened with KMC_SEEN_SET_SPREAD=16 owns sixteen times its table for a moment; after kmc_open the device's free memory
-    is down by the handle's own buffers only (own process: the factor is read once)."""
+    is down by the handle's own buffers only (a process of its own: the free memory it measures is its own)."""
     code = (
         "import ctypes, os\n"
         "from kafka_specification_amd import CheckerConfig, ModelChecker\n"

@@ -385,12 +385,12 @@ def test_sender_side_filter_drops_duplicates_but_not_states():
     dropped = sharded.run_sharded.last_send_filtered
     assert (r.distinct, r.generated, r.levels) == (o.distinct, o.generated, o.levels)
     assert dropped > o.generated // 10        # g = 2.8 here: most remote copies are duplicates
-    os.environ["KMC_NO_SEND_FILTER"] = "1"
+    os.environ["KMC_SEND_FILTER"] = "0"
     try:
         r2 = check_loopback(cfg, 3)
         assert sharded.run_sharded.last_send_filtered == 0
     finally:
-        del os.environ["KMC_NO_SEND_FILTER"]
+        del os.environ["KMC_SEND_FILTER"]
     assert (r2.distinct, r2.generated, r2.levels) == (r.distinct, r.generated, r.levels)
 
 

@@ -7,7 +7,8 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export KMC_NO_TORCH=1
 CMD="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
-KMC_DRYRUN=1 $CMD 2>&1 | grep "kmc\]" | tee "$OUT/dry.log"
+# (the dry pass needs both halves of a tuning build; the traces below run the shipped library and kernels)
+KMC_LIB_PATH="$REPO/kafka_specification_amd/libkmc_tuning.so" KMC_JIT_DEFINES="-DKMC_TUNING=1" KMC_DRYRUN=1 $CMD 2>&1 | grep "kmc\]" | tee "$OUT/dry.log"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $CMD > "$OUT/trace.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d "$OUT/pmc1" -o pmc -- $CMD > "$OUT/pmc1.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_WAIT_INST_LDS --output-format csv -d "$OUT/pmc2" -o pmc -- $CMD > "$OUT/pmc2.log" 2>&1

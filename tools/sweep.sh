@@ -4,6 +4,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export KMC_NO_TORCH=1
+export KMC_LIB_PATH="$PWD/kafka_specification_amd/libkmc_tuning.so"   # KMC_BLOCKS_PER_CU is an aid of the tuning build
 for spec in "$@"; do
   IFS='|' read -r name defs bpc <<< "$spec"
   export KMC_JIT_DEFINES="$defs"
