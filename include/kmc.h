@@ -376,6 +376,40 @@ int kmc_exchange_plan(const uint64_t* counts, int32_t n_shards, int32_t me, uint
                       uint64_t* sends, uint64_t* recvs, uint64_t cap, uint64_t* n_sends, uint64_t* n_recvs,
                       uint64_t* recv_records);
 
+/* --- front end: what a .cfg, a spec file, a state and a stock-TLC switch mean (csrc/kmc_frontend.cpp) ------------
+ * The one copy of what both tlc-shaped command lines (kafka_specification_amd/tlc.py, csrc/kmc_cli.cpp) decide
+ * outside their main loops.  Plain host code: no device, no handle, no environment variable. */
+/* Read a TLC model configuration (CONSTANT(S), INIT, NEXT, SPECIFICATION, INVARIANT(S), CHECK_DEADLOCK, CONSTRAINT
+ * StateConstraint for MCAsyncIsr; comments) and bind it to the lowered model of root module `module`: fills model, the
+ * constants of that model's family, invariant_mask and check_deadlock, and leaves every other field as the caller set
+ * it.  KMC_E_ARG with the reason in kmc_last_error() for whatever the lowering cannot honour. */
+int kmc_cfg_bind(const char* module, const char* cfg_text, kmc_config* out);
+/* Identity of the spec text: sha256 of spec_path and of every module it EXTENDS / INSTANCEs that lies beside it, against
+ * the revision of hachikuji/kafka-specification the kernels were lowered from (MCAsyncIsr, authored here: against
+ * ../models/MCAsyncIsr.tla relative to this library's file).  0 = every module found matches, 1 = spec_path does not
+ * exist, 2 = a module differs or is unknown; msgs receives the findings, one per line (cut to cap). */
+int kmc_spec_check(const char* spec_path, char* msgs, uint64_t cap);
+/* Canonical bytes (above) as TLA+ text, the way TLC prints a trace state; lines joined by '\n', no trailing one.
+ * Returns the length of the whole text (out receives at most cap - 1 characters and a 0), or -1 (kmc_last_error) when
+ * cfg's constants are out of range or canon_len is shorter than their layout. */
+int64_t kmc_format_state(const kmc_config* cfg, const uint8_t* canon, uint64_t canon_len, char* out, uint64_t cap);
+/* A switch of stock TLC that this engine has no use for [TLC-recall]: its class, and why (NULL for KMC_SWITCH_NONE). */
+#define KMC_SWITCH_NONE 0          /* not a stock switch: the front end's own business */
+#define KMC_SWITCH_IGNORED 1       /* changes nothing that is checked: accepted with a note */
+#define KMC_SWITCH_IGNORED_VALUE 2 /* ... and takes a value */
+#define KMC_SWITCH_REFUSED 3       /* asks for another mode of operation: the run ends with status 2 */
+const char* kmc_tlc_switch(const char* flag, int32_t* switch_class);
+/* TLC's closing estimate of a silent fingerprint collision [TLC-recall], as printed lines joined by '\n'.
+ * orbit_representatives != 0 (a symmetry search): the seen-set holds the representatives, so they are what is
+ * counted.  A search that ended well (finished_ok) on 64-bit entries whose birthday bound exceeds
+ * KMC_FP128_ADVICE_ABOVE has no certified count: the text then ends with the warning and the return value is
+ * KMC_EXIT_UNCERTIFIED, the status both front ends exit with; 0 otherwise. */
+#define KMC_FP128_ADVICE_ABOVE 0.1
+#define KMC_EXIT_UNCERTIFIED 14
+int kmc_collision_report(uint64_t distinct, uint64_t generated, uint64_t orbit_representatives, int32_t wide,
+                         int32_t finished_ok, char* out, uint64_t cap);
+int32_t kmc_uncertified_policy(double* advice_above);   /* the two numbers above, for a binding: returns the status */
+
 #ifdef __cplusplus
 }
 #endif

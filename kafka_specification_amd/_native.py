@@ -14,6 +14,7 @@ KMC_SYMMETRY_MAX_REPLICAS = 7
 KMC_SEND_SUBS = 8
 KMC_COMM_ID_BYTES = 128
 KMC_EXCHANGE_STATS = 64
+KMC_SWITCH_NONE, KMC_SWITCH_IGNORED, KMC_SWITCH_IGNORED_VALUE, KMC_SWITCH_REFUSED = range(4)   # kmc_tlc_switch
 
 MODELS = {
     "IdSequence": 0,
@@ -151,6 +152,13 @@ SYMBOLS = [
     ("kmc_exchange_plan", C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # the front end (csrc/kmc_frontend.cpp): cfg.py, spec_revision.py, format.py and tlc.py are its callers
+    ("kmc_cfg_bind", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(KmcConfig)]),
+    ("kmc_spec_check", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64]),
+    ("kmc_format_state", C.c_int64, [C.POINTER(KmcConfig), C.POINTER(C.c_uint8), C.c_uint64, C.c_char_p, C.c_uint64]),
+    ("kmc_tlc_switch", C.c_char_p, [C.c_char_p, C.POINTER(C.c_int32)]),
+    ("kmc_collision_report", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
+    ("kmc_uncertified_policy", C.c_int32, [C.POINTER(C.c_double)]),
 ]
 
 _lib = None

@@ -835,6 +835,11 @@ def bench_sharded(c: dict, steps: int, warmup: int, backend: str = "nccl", symme
                            "(there is no CPU fallback)")
     if not dist.is_initialized():
         dist.init_process_group(backend=backend)
+        if not on_gpu:
+            # a gloo group that is still alive when the interpreter exits takes its threads down in no order: now and then a
+            # rank that has printed its result ends in std::terminate ("terminate called without an active exception")
+            import atexit
+            atexit.register(lambda: dist.is_initialized() and dist.destroy_process_group())
     rank, world = dist.get_rank(), dist.get_world_size()
     local = int(os.environ.get("LOCAL_RANK", rank))
     if on_gpu:

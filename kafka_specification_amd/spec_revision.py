@@ -7,78 +7,21 @@ hachikuji/kafka-specification the lowering was written against.  A mismatch is r
 file that does not exist (this repository ships no copy of the reference's .tla files) is reported and the built-in
 lowering is checked.
 
-SHA256 holds sha256 of each reference module (generated by `sha256sum /root/reference/*.tla`; the C++ front end carries
-the same table in csrc/kmc_cli.cpp).  models/MCAsyncIsr.tla is authored in this repository and hashed at run time
-against the copy in models/.
+The table of hashes, the walk and the SHA-256 are the library's (csrc/kmc_frontend.cpp: kmc_spec_check); models/MCAsyncIsr.tla
+is authored in this repository and hashed at run time against the copy in models/.
 """
 from __future__ import annotations
 
-import hashlib
-import os
-import re
+import ctypes as C
 
-SHA256 = {
-    "AsyncIsr": "6c29fa0de4174c9a36b1b933b43df115f53254f727cdf6b05b1c6306e77f3e46",
-    "FiniteReplicatedLog": "cc6193fcc9bc75be6ce2b4ab9719d9bb645c0e0441e53fda630097e13edde747",
-    "IdSequence": "bf8a9f74c8ccad8aa2ee4139df4297942f9a8a429afffb2e1f032833b6912654",
-    "KafkaReplication": "80fffc6c9e430106cb0be059f542239fa85079ffe5834493f96cbadfe122ed9a",
-    "KafkaTruncateToHighWatermark": "97b38e8c1d41113173784cee59c884b54554a9608ac7ddad442f80eed7af6d35",
-    "Kip101": "77a8ea39557ae7e19c975eb62cc1b4253761a22426c562c1e891fc361f918f6f",
-    "Kip279": "9568ffd395b77367722757b8a3aab999b682ab657e4fb13d41629c3696b4e39f",
-    "Kip320": "4f2dccca13414af26dbebeffbdb105b46973f55c79a46c04be76cde73aa963ca",
-    "Kip320FirstTry": "b2985bc5dad379d15cc88e838f0e3bce8e232a52a197c7f5dcd941821467d705",
-    "Util": "56a9514e28ac684657a91456f1f8985351bf23c9ec29d65e69a65987cfc9b385",
-}
-STANDARD_MODULES = {"Integers", "Naturals", "Sequences", "FiniteSets", "TLC", "Reals", "Bags"}
-# authored here; its expected hash is that of the file in this repository's models/ directory
-LOCAL_MODULES = {"MCAsyncIsr": os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models",
-                                            "MCAsyncIsr.tla")}
+from . import _native as nat
 
-
-def imports_of(text: str):
-    """Module names a module EXTENDS or INSTANCEs (comments stripped)."""
-    text = re.sub(r"\(\*.*?\*\)", " ", text, flags=re.S)
-    text = "\n".join(line.split("\\*")[0] for line in text.splitlines())
-    names = []
-    for m in re.finditer(r"\bEXTENDS\b([^\n]*)", text):
-        names += [n.strip() for n in m.group(1).split(",") if n.strip()]
-    names += re.findall(r"\bINSTANCE\s+(\w+)", text)
-    return [n for n in names if re.fullmatch(r"\w+", n)]
-
-
-def expected_sha256(module: str):
-    if module in SHA256:
-        return SHA256[module]
-    if module in LOCAL_MODULES and os.path.exists(LOCAL_MODULES[module]):
-        return hashlib.sha256(open(LOCAL_MODULES[module], "rb").read()).hexdigest()
-    return None
+STATUS = ("ok", "absent", "mismatch")
 
 
 def check_spec(path: str):
     """-> (status, messages).  status: "ok" every module of the closure that exists matches the lowered revision;
     "absent" the root module file does not exist; "mismatch" some module differs or is unknown."""
-    if not os.path.exists(path):
-        return "absent", [f"{path} does not exist: checking the built-in lowering of "
-                          f"{os.path.splitext(os.path.basename(path))[0]} (reference revision, sha256 table in spec_revision.py)"]
-    here = os.path.dirname(os.path.abspath(path))
-    todo, seen, msgs, bad = [os.path.splitext(os.path.basename(path))[0]], set(), [], False
-    while todo:
-        mod = todo.pop()
-        if mod in seen or mod in STANDARD_MODULES:
-            continue
-        seen.add(mod)
-        f = os.path.join(here, mod + ".tla")
-        if not os.path.exists(f):
-            msgs.append(f"module {mod}: {f} not found (not verified)")
-            continue
-        data = open(f, "rb").read()
-        want, got = expected_sha256(mod), hashlib.sha256(data).hexdigest()
-        if want is None:
-            msgs.append(f"module {mod}: not a module of the lowered revision")
-            bad = True
-        elif want != got:
-            msgs.append(f"module {mod}: {f} differs from the revision the kernels were lowered from "
-                        f"(sha256 {got[:16]}…, expected {want[:16]}…)")
-            bad = True
-        todo += imports_of(data.decode("utf-8", "replace"))
-    return ("mismatch" if bad else "ok"), msgs
+    msgs = C.create_string_buffer(16384)
+    status = nat.lib().kmc_spec_check(path.encode(), msgs, len(msgs))
+    return STATUS[status], msgs.value.decode("utf-8", "replace").splitlines()

@@ -19,10 +19,12 @@ time with another fingerprint seed and compares the counts (a collision moves wi
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import os
 import sys
 import time
 
+from . import _native as nat
 from .cfg import CfgError, parse_cfg, to_checker_config
 from .checker import ModelChecker
 from .format import format_state
@@ -32,58 +34,31 @@ def _now():
     return time.strftime("%Y-%m-%d %H:%M:%S")
 
 
+def _collision(distinct, generated, representatives, wide, finished_ok):
+    """(lines, exit status or 0) of the library's kmc_collision_report (include/kmc.h): TLC's closing estimate, the advice to
+    use -fp128 above FP128_ADVICE_ABOVE, and the warning with UNCERTIFIED_EXIT_CODE for a finished search above it."""
+    out = C.create_string_buffer(2048)
+    rc = nat.lib().kmc_collision_report(distinct, generated, representatives, int(wide), int(finished_ok), out, len(out))
+    return out.value.decode().splitlines(), rc
+
+
 def collision_report(distinct: int, generated: int, wide: bool = False):
-    """TLC's closing estimate [TLC-recall: "calculated (optimistic)" = distinct x (generated - distinct) / 2^64], plus
-    the birthday bound n^2 / 2^65 for the fingerprints that were stored.  With -fp128 every entry also holds a second,
-    independent 64-bit hash of the state: two states are only merged when both words agree."""
-    if wide:
-        return ["The seen-set stores 128 bits per state (the fingerprint and an independent check word); probability that two "
-                "distinct states were merged:",
-                f"  birthday bound on the stored entries:  val = {distinct * distinct / 2.0 ** 129:.2E}"]
-    opt = distinct * max(generated - distinct, 0) / 2.0 ** 64
-    birthday = distinct * distinct / 2.0 ** 65
-    out = ["The seen-set stores 64-bit fingerprints; estimates of the probability that not all reachable states were "
-           "checked because two distinct states had the same fingerprint:",
-           f"  calculated (optimistic):  val = {opt:.2E}",
-           f"  birthday bound on the stored fingerprints:  val = {birthday:.2E}"]
-    if birthday > FP128_ADVICE_ABOVE:
-        # (Kip320 3/6/6/3: 6,452,700,520 states, birthday bound 1.1 — the 64-bit search returns one state fewer)
-        out.append(f"  Recommendation: that bound is above {FP128_ADVICE_ABOVE}: counts of this size are only bit-exact with 128-bit "
-                   "entries - re-run with -fp128 (or, on the Kafka modules, -symmetry: a sixth of the stored fingerprints at three brokers).")
-    return out
+    return _collision(distinct, generated, 0, wide, False)[0]
 
 
 def uncertified(distinct: int, wide: bool) -> bool:
     """A finished 64-bit search whose birthday bound exceeds FP128_ADVICE_ABOVE: its distinct-state count is more likely to be
     off than not (BASELINE's target is the bit-identical count) — both front ends then exit with UNCERTIFIED_EXIT_CODE."""
-    return (not wide) and distinct * distinct / 2.0 ** 65 > FP128_ADVICE_ABOVE
+    return _collision(distinct, distinct, 0, wide, True)[1] != 0
 
 
-UNCERTIFIED_EXIT_CODE = 14
-
-
-FP128_ADVICE_ABOVE = 0.1
-
-
-TLC_IGNORED_FLAGS = {
-    "-modelcheck": "model checking is the only mode", "-cleanup": "no states directory is written",
-    "-nowarning": "no TLA+ is evaluated, so no evaluation warnings exist", "-terse": "values are printed in full",
-    "-tool": "no tool-mode message codes", "-gzip": "checkpoints are not compressed", "-debug": "no debug output",
-    "-noGenerateSpecTE": "no trace-expression spec is generated", "-difftrace": "traces print every variable of every state",
-}
-TLC_IGNORED_WITH_VALUE = {
-    "-metadir": "nothing is written there", "-userFile": "the lowered models print nothing",
-    "-fpmem": "the fingerprint table lives in HBM: -table SLOTS sizes it", "-fpbits": "one table, no partitioning by bits",
-    "-maxSetSize": "no set is enumerated at run time", "-coverage": "action coverage is not collected",
-    "-lncheck": "no liveness checking",
-}
-TLC_REFUSED_FLAGS = {
-    "-simulate": "random simulation is another mode of TLC; only exhaustive breadth-first model checking is implemented",
-    "-depth": "it belongs to -simulate", "-seed": "it belongs to -simulate", "-aril": "it belongs to -simulate",
-    "-dump": "the reachable states stay on the GPU (kmc_frontier_states gives a level's states through the C ABI)",
-    "-view": "a VIEW changes the distinct-state count", "-dfid": "depth-first iterative deepening is another search order",
-    "-generateSpecTE": "no trace-expression spec is generated",
-}
+def __getattr__(name):
+    """UNCERTIFIED_EXIT_CODE, FP128_ADVICE_ABOVE: the library's numbers (include/kmc.h), read when first asked for."""
+    if name in ("UNCERTIFIED_EXIT_CODE", "FP128_ADVICE_ABOVE"):
+        above = C.c_double()
+        code = nat.lib().kmc_uncertified_policy(C.byref(above))
+        return code if name == "UNCERTIFIED_EXIT_CODE" else above.value
+    raise AttributeError(name)
 
 
 def main(argv=None) -> int:
@@ -131,18 +106,21 @@ def main(argv=None) -> int:
     # Stock TLC's other command-line switches [TLC-recall]: the ones that do not change what is checked are accepted and
     # ignored with a note (a wrapper script written for `java tlc2.TLC` keeps working); the ones that ask for another mode
     # of operation are refused — silently dropping them would answer a different question than the one asked.
+    # Which is which, and why: the library's kmc_tlc_switch.
     argv = list(sys.argv[1:] if argv is None else argv)
     kept, i = [], 0
     while i < len(argv):
         t = argv[i]
-        if t in TLC_IGNORED_FLAGS:
-            print(f"Note: {t} is accepted for compatibility and ignored ({TLC_IGNORED_FLAGS[t]})", file=sys.stderr)
-        elif t in TLC_IGNORED_WITH_VALUE:
+        kind = C.c_int32()
+        why = (nat.lib().kmc_tlc_switch(t.encode(), C.byref(kind)) or b"").decode()
+        if kind.value == nat.KMC_SWITCH_IGNORED:
+            print(f"Note: {t} is accepted for compatibility and ignored ({why})", file=sys.stderr)
+        elif kind.value == nat.KMC_SWITCH_IGNORED_VALUE:
             print(f"Note: {t} {argv[i + 1] if i + 1 < len(argv) else ''} is accepted for compatibility and ignored "
-                  f"({TLC_IGNORED_WITH_VALUE[t]})", file=sys.stderr)
+                  f"({why})", file=sys.stderr)
             i += 1
-        elif t in TLC_REFUSED_FLAGS:
-            print(f"Error: {t} is not supported: {TLC_REFUSED_FLAGS[t]}", file=sys.stderr)
+        elif kind.value == nat.KMC_SWITCH_REFUSED:
+            print(f"Error: {t} is not supported: {why}", file=sys.stderr)
             return 2
         elif (t == "-checkpoint" and i + 1 < len(argv) and argv[i + 1].lstrip("-").isdigit()
               and not os.path.isdir(argv[i + 1])):
@@ -213,7 +191,6 @@ def main(argv=None) -> int:
             print(f"Progress({i['depth']}) at {_now()}: {i['generated']} states generated, "
                   f"{i['distinct']} distinct states found, {i['new_states']} states left on queue.")
 
-    from ._native import KmcError
     from dataclasses import replace
 
     def search(conf, progress):
@@ -246,7 +223,7 @@ def main(argv=None) -> int:
             seed2 = (a.fp * 0x9E3779B97F4A7C15 + 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
             second, _ = search(replace(cc, hash_seed=seed2, keep_trace=False), None)
             second = (seed2, second)
-    except KmcError as e:
+    except nat.KmcError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 3
 
@@ -277,17 +254,9 @@ def main(argv=None) -> int:
     if a.symmetry:
         print(f"Symmetry reduction (orbit counting over the permutations of Replicas): {res.orbit_representatives} states "
               f"were stored and expanded, one per orbit; every count above is the plain search's.")
-    # (the seen-set holds the representatives: they are what can collide, and what was probed for)
-    stored, probed = res.distinct, res.generated
-    if a.symmetry and res.distinct:
-        stored = res.orbit_representatives
-        probed = res.generated * stored // res.distinct
-    for line in collision_report(stored, probed, a.fp128):
-        print(line)
-    if rc == 0 and uncertified(stored, a.fp128):
-        print(f"Warning: the distinct-state count of this run is NOT certified (64-bit fingerprints, birthday bound "
-              f"{stored * stored / 2.0 ** 65:.2E} > {FP128_ADVICE_ABOVE}): exit code {UNCERTIFIED_EXIT_CODE}.")
-        rc = UNCERTIFIED_EXIT_CODE
+    lines, uncertified_rc = _collision(res.distinct, res.generated, res.orbit_representatives if a.symmetry else 0, a.fp128, rc == 0)
+    print("\n".join(lines))
+    rc = uncertified_rc or rc
     if a.levels_csv and level_rows is not None:
         names = list(res.action_generated)
         with open(a.levels_csv, "w") as lf:

@@ -1,6 +1,7 @@
 """Host logic that needs no GPU: the .cfg reader, its binding to the lowered models, the state
 pretty-printer and the CLI's error paths."""
 import glob
+import json
 import os
 
 import pytest
@@ -39,9 +40,14 @@ def test_cfg_syntax():
         SPECIFICATION Spec
         INVARIANT TypeOk
     ''')
-    assert m.constants == {"MaxId": 7} and m.specification == "Spec" and m.invariants == ["TypeOk"]
+    # (the text is read when it is bound — csrc/kmc_frontend.cpp: what used to be looked up in the parse tree is looked up in
+    # the binding: the constant, the invariant, SPECIFICATION Spec accepted and any other refused)
     c = to_checker_config("IdSequence", m)
-    assert c.max_id == 7 and c.check_deadlock is True  # TLC checks deadlock unless told otherwise
+    assert c.max_id == 7 and c.invariants == ("TypeOk",) and c.model == "IdSequence"
+    assert c.check_deadlock is True  # TLC checks deadlock unless told otherwise
+    assert to_checker_config("IdSequence", parse_cfg(m.replace("INVARIANT TypeOk", ""))).invariants == ()
+    with pytest.raises(CfgError, match="only SPECIFICATION Spec is known"):
+        to_checker_config("IdSequence", parse_cfg(m.replace("SPECIFICATION Spec", "SPECIFICATION Other")))
     m = parse_cfg("CONSTANTS Replicas = {a, b}\n LogRecords = {x}\n Nil = nil\n LogSize = 3\nCHECK_DEADLOCK FALSE")
     c = to_checker_config("FiniteReplicatedLog", m)
     assert (c.n_replicas, c.n_log_records, c.log_size, c.check_deadlock) == (2, 1, 3, False)
@@ -117,15 +123,32 @@ def test_native_cli_error_paths(tmp_path):
         assert r.returncode == 3 and "no CPU fallback" in r.stderr  # fails loudly without a GPU
 
 
-def _both_clis(args):
+def _both_clis(args, **environment):
     """(returncode, stderr) of the Python and the native front end."""
     import subprocess
     import sys
     exe = os.path.join(ROOT, "kafka_specification_amd", "tlc")
-    env = dict(os.environ, PYTHONPATH=ROOT)
+    env = dict(os.environ, PYTHONPATH=ROOT, **environment)
     py = subprocess.run([sys.executable, "-m", "kafka_specification_amd.tlc"] + args, capture_output=True, text=True, env=env)
     cc = subprocess.run([exe] + args, capture_output=True, text=True)
     return (py.returncode, py.stderr), (cc.returncode, cc.stderr)
+
+
+REFUSED = [r for r in json.load(open(os.path.join(ROOT, "tests", "golden", "frontend_parity.json")))["refusals"] if not r["accepted"]]
+
+
+@pytest.mark.parametrize("k", range(len(REFUSED)))
+def test_both_front_ends_refuse_with_one_text(tmp_path, k):
+    """Every refused .cfg text of tests/golden/frontend_parity.json (the rejection tests' own and the cases the two readers used
+    to tell apart: test_frontend_parity_cpu.py) through both executables: status 2 and the same single `Error:` line, nothing
+    else.  (A refused .cfg ends either process before it touches a device: the Python one is started without PyTorch's runtime,
+    which keeps a case at a fraction of a second.)"""
+    cfg = tmp_path / "x.cfg"
+    cfg.write_text(REFUSED[k]["text"])
+    (prc, perr), (crc, cerr) = _both_clis(["-config", str(cfg), "-deadlock", str(tmp_path / (REFUSED[k]["module"] + ".tla"))],
+                                          KMC_NO_TORCH="1")
+    assert prc == crc == 2, (perr, cerr)
+    assert perr == cerr and perr.startswith("Error: ") and perr.count("\n") == 1, (perr, cerr)
 
 
 def test_spec_identity_guard_refuses_an_edited_spec(tmp_path):
@@ -143,7 +166,7 @@ def test_spec_identity_guard_refuses_an_edited_spec(tmp_path):
     digest = hashlib.sha256(spec.read_bytes()).hexdigest()[:16]
     for rc, err in _both_clis([str(spec), "-deadlock", "-table", "1024", "-frontier", "1024"]):
         assert rc == 2 and "differs from the revision" in err and "nothing was checked" in err
-        assert digest in err                       # both front ends hash the same bytes (the C++ one with its own SHA-256)
+        assert digest in err                       # the library's own SHA-256 (csrc/kmc_frontend.cpp) against hashlib's
     if no_gpu:
         for rc, err in _both_clis([str(spec), "-deadlock", "-force", "-table", "1024", "-frontier", "1024"]):
             assert rc == 3 and "-force" in err and "no CPU fallback" in err      # past the guard, then no device

@@ -85,3 +85,25 @@ def test_the_device_model_templates_are_clean_under_asan_and_ubsan(sanitized_emu
         assert j["violating_states"] == o.viol_count[invs[0]]
     assert j["kind_major_bindings_bad"] == 0
     o.close()
+
+
+def test_the_front_end_is_clean_under_asan_and_ubsan(tmp_path):
+    """csrc/kmc_frontend.cpp — the .cfg reader, the state printer, the spec walk's buffers — compiled ALONE with the stand-alone
+    tests/frontend_san.cpp and instrumented: every shipped .cfg, every text of tests/golden/frontend_parity.json and every cut of
+    each, texts that end inside a set / a comment / a string, buffers of 0 and 1 bytes, states at the largest constants."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "frontend_parity.json")))
+    exe = str(tmp_path / "frontend_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "frontend_san.cpp"),
+                           os.path.join(ROOT, "kafka_specification_amd", "csrc", "kmc_frontend.cpp"), "-ldl"])
+    args = []
+    for name, b in sorted(golden["bindings"].items()):
+        args += [b["module"], os.path.join(ROOT, "models", name), "1"]
+    for k, r in enumerate(golden["refusals"]):
+        (tmp_path / f"{k}.cfg").write_text(r["text"])
+        args += [r["module"], str(tmp_path / f"{k}.cfg"), str(int(r["accepted"]))]
+    p = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1"))
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
+    assert not any(r in p.stderr for r in REPORTS), p.stderr[-3000:]
+    assert p.stdout.splitlines()[-1] == f"{len(golden['bindings']) + 8} bound, 36 refused, 0 unexpected"
