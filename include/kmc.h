@@ -202,9 +202,12 @@ int kmc_open(const kmc_config* cfg, kmc_handle** out);
  * kernels around it: kmc_run needs nothing else), k_expand for the level-step interface (owner bucketing: kmc_step_*) and
  * k_expand as an enumerator (kmc_successors, trace replay) — the last two joining a handle when first asked for.
  * kmc_precompile builds all three; kmc_precompile_mode one of them (mode 0 / 1 / 2 in that order, -1 = all), so that a build
- * script can spread them over its workers. */
+ * script can spread them over its workers.  The fourth object, k_simulate (random simulation, below), is asked for by name:
+ * kmc_precompile_simulate, for the configurations that are walked; its cached file is tagged -simulate the way the others are
+ * tagged -sharded / -enum. */
 int kmc_precompile(const kmc_config* cfg, const char* arch);
 int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode);
+int kmc_precompile_simulate(const kmc_config* cfg, const char* arch);
 /* Path of the cached code object cfg's kernels are loaded from (specialised first if absent; no GPU needed).  A profile
  * records a hash of its kernels' machine code, so that a number is quoted only for the code it was measured on. */
 int kmc_code_object_path(const kmc_config* cfg, const char* arch, char* out, uint64_t cap);
@@ -376,6 +379,60 @@ int kmc_exchange_plan(const uint64_t* counts, int32_t n_shards, int32_t me, uint
                       uint64_t* sends, uint64_t* recvs, uint64_t cap, uint64_t* n_sends, uint64_t* n_recvs,
                       uint64_t* recv_records);
 
+/* --- random simulation: batched random walks (TLC's -simulate analogue [TLC-recall]; csrc/kmc_sim.h, kmc_sim_engine.cpp) -----
+ * A walk is a pure function of the model constants, `seed` and the walk's index w — never of the batch, the grid or the
+ * device.  State 0 is Init.  At step t the walk stands on state s_t; its candidates are TLC's enumeration of Next on s_t,
+ * exactly the records kmc_successors lists (n_t of them; a successor two disjuncts of one binding yield counts twice); it
+ * takes record r_t = kmc_sim_draw(seed, w, t, n_t) of them, in an order of its own that is the same for every walk standing
+ * on that state.  Every state, Init and the last one included, is checked against cfg.invariant_mask.  The walk ends at the
+ * first of: a violating state; a state with n_t = 0 (a deadlock under check_deadlock, else just the walk's end); `depth`
+ * states (the last of them is checked, its successors are not looked at).
+ * Walks run in launches of walks_per_launch, every walker to its own end.  Without continue_on_violation the first launch
+ * that holds a violation or checked deadlock is the last one, and the witness is the smallest walk index among that launch's
+ * ending-in-a-verdict walks, at that walk's own last step.  With it every launch runs, the violations are counted per
+ * invariant, and the witness is that of the first launch that holds one.
+ * Not for KMC_ASYNC_ISR (which successors outside the state constraint are candidates is undecided) nor for handles opened
+ * with `symmetry` (a walk is of real states): KMC_E_ARG. */
+typedef struct kmc_sim_config {
+    uint64_t seed;
+    uint64_t first_walk;        /* index of the batch's first walk */
+    uint64_t n_walks;
+    uint32_t depth;             /* states per walk at the most; 0 = 100 (TLC's -depth default) */
+    uint32_t walks_per_launch;  /* 0 = 2^20 */
+    int32_t record;             /* 1: keep every state of every walk of the batch on the device for kmc_simulate_walk (bounded:
+                                   KMC_E_ARG beyond KMC_SIM_RECORD_MAX_BYTES) */
+    int32_t pad_;
+} kmc_sim_config;
+#define KMC_SIM_RECORD_MAX_BYTES (1ull << 30)
+
+typedef struct kmc_sim_result {
+    uint64_t walks;             /* walks run */
+    uint64_t states_generated;  /* every state a walk stood on, the initial states included */
+    uint64_t action_taken[KMC_MAX_KINDS]; /* steps taken per Next disjunct, in the module's order */
+    uint64_t ended_early;       /* walks that ended on a state without successors */
+    uint64_t longest_walk;      /* states of the longest walk */
+    int32_t verdict;            /* KMC_V_OK / KMC_V_INVARIANT / KMC_V_DEADLOCK */
+    int32_t violated_invariant; /* index 0..3 of the witness's (lowest) violated invariant, -1 = none */
+    uint64_t violation_walk;    /* the witness: walk index ... */
+    uint64_t violation_step;    /* ... and the 0-based step (Init is step 0) of its violating / deadlocked state */
+    uint64_t violation_count[4];/* walks that ended on a state violating each invariant */
+    uint64_t launches;
+    double seconds_total;       /* wall time of kmc_simulate */
+    double seconds_kernel;      /* sum of the k_simulate launches' durations (HIP events on the engine stream) */
+} kmc_sim_result;
+
+/* Runs the batch.  The kernels' fourth code object (k_simulate: kmc_precompile_simulate) joins the handle on the first call.
+ * The seen-set and the frontiers are not touched. */
+int kmc_simulate(kmc_handle* h, const kmc_sim_config* sim, kmc_sim_result* out);
+/* One walk as data: per state s_0 .. s_(len-1) its canonical bytes, the action kind that produced it (-1 for Init), the
+ * record r chosen and the number of candidates it was chosen among on the state before (0, 0 for Init).  Read from the last
+ * recorded batch (same seed and depth) when the walk is in it, else that one walker is re-run in record mode: the two agree.
+ * Of `sim` only seed and depth are read.  Fills up to cap entries; *n_out = the walk's states. */
+int kmc_simulate_walk(kmc_handle* h, const kmc_sim_config* sim, uint64_t walk, uint8_t* canon_states, int32_t* kinds,
+                      uint32_t* choice, uint32_t* n_enabled, uint64_t cap, uint64_t* n_out);
+/* The draw: a fixed 64-bit mix of (seed, walk, step) reduced by multiply-high to 0..n-1 (0 for n = 0).  Pure, no handle. */
+uint64_t kmc_sim_draw(uint64_t seed, uint64_t walk, uint32_t step, uint32_t n);
+
 /* --- front end: what a .cfg, a spec file, a state and a stock-TLC switch mean (csrc/kmc_frontend.cpp) ------------
  * The one copy of what both tlc-shaped command lines (kafka_specification_amd/tlc.py, csrc/kmc_cli.cpp) decide
  * outside their main loops.  Plain host code: no device, no handle, no environment variable. */
@@ -409,6 +466,16 @@ const char* kmc_tlc_switch(const char* flag, int32_t* switch_class);
 int kmc_collision_report(uint64_t distinct, uint64_t generated, uint64_t orbit_representatives, int32_t wide,
                          int32_t finished_ok, char* out, uint64_t cap);
 int32_t kmc_uncertified_policy(double* advice_above);   /* the two numbers above, for a binding: returns the status */
+/* Random simulation on the command lines: -walks N [-walk-depth D] [-walk-seed S] (stock TLC's -simulate / -depth / -seed stay
+ * refused).  Each argument is the text that followed its switch, NULL when the switch was not given.  *asked = 1 and n_walks /
+ * depth / seed of *out filled when -walks was given; KMC_E_ARG with the reason in kmc_last_error() for -walks 0, a value that is
+ * no whole number, or -walk-depth / -walk-seed without -walks. */
+int kmc_walk_switches(const char* walks, const char* depth, const char* seed, kmc_sim_config* out, int32_t* asked);
+/* What both command lines print around a batch: closing = 0 the opening line (res may be NULL), 1 the lines after the batch,
+ * action_names[0 .. n_actions-1] (kmc_action_name) heading the per-action step counts.  Lines joined by '\n'; returns the
+ * length of the whole text, -1 on a null argument. */
+int64_t kmc_sim_report(const kmc_config* cfg, const kmc_sim_config* sim, const kmc_sim_result* res, int32_t closing,
+                       const char* const* action_names, int32_t n_actions, char* out, uint64_t cap);
 
 #ifdef __cplusplus
 }

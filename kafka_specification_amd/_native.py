@@ -89,6 +89,19 @@ class KmcLevelStat(C.Structure):
                 ("table_load", C.c_double), ("expand_ms", C.c_double)]
 
 
+class KmcSimConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_walk", C.c_uint64), ("n_walks", C.c_uint64), ("depth", C.c_uint32),
+                ("walks_per_launch", C.c_uint32), ("record", C.c_int32), ("pad_", C.c_int32)]
+
+
+class KmcSimResult(C.Structure):
+    _fields_ = [("walks", C.c_uint64), ("states_generated", C.c_uint64), ("action_taken", C.c_uint64 * KMC_MAX_KINDS),
+                ("ended_early", C.c_uint64), ("longest_walk", C.c_uint64), ("verdict", C.c_int32),
+                ("violated_invariant", C.c_int32), ("violation_walk", C.c_uint64), ("violation_step", C.c_uint64),
+                ("violation_count", C.c_uint64 * 4), ("launches", C.c_uint64), ("seconds_total", C.c_double),
+                ("seconds_kernel", C.c_double)]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.POINTER(KmcLevelInfo), C.c_void_p)
 
 # every symbol include/kmc.h declares: (name, restype, argtypes)
@@ -97,6 +110,7 @@ SYMBOLS = [
     ("kmc_open", C.c_int, [C.POINTER(KmcConfig), C.POINTER(_H)]),
     ("kmc_precompile", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
     ("kmc_precompile_mode", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_int32]),
+    ("kmc_precompile_simulate", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
     ("kmc_code_object_path", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_char_p, C.c_uint64]),
     ("kmc_run", C.c_int, [_H, PROGRESS_CB, C.c_void_p]),
     ("kmc_result_get", C.c_int, [_H, C.POINTER(KmcResult)]),
@@ -152,6 +166,11 @@ SYMBOLS = [
     ("kmc_exchange_plan", C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # random simulation (csrc/kmc_sim_engine.cpp)
+    ("kmc_simulate", C.c_int, [_H, C.POINTER(KmcSimConfig), C.POINTER(KmcSimResult)]),
+    ("kmc_simulate_walk", C.c_int, [_H, C.POINTER(KmcSimConfig), C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("kmc_sim_draw", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
     # the front end (csrc/kmc_frontend.cpp): cfg.py, spec_revision.py, format.py and tlc.py are its callers
     ("kmc_cfg_bind", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(KmcConfig)]),
     ("kmc_spec_check", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64]),
@@ -159,6 +178,9 @@ SYMBOLS = [
     ("kmc_tlc_switch", C.c_char_p, [C.c_char_p, C.POINTER(C.c_int32)]),
     ("kmc_collision_report", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
     ("kmc_uncertified_policy", C.c_int32, [C.POINTER(C.c_double)]),
+    ("kmc_walk_switches", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(KmcSimConfig), C.POINTER(C.c_int32)]),
+    ("kmc_sim_report", C.c_int64, [C.POINTER(KmcConfig), C.POINTER(KmcSimConfig), C.POINTER(KmcSimResult), C.c_int32,
+                                   C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_uint64]),
 ]
 
 _lib = None

@@ -96,11 +96,39 @@ class CheckResult:
     inv_launches: int = 0
 
 
+@dataclass
+class SimulateResult:
+    walks: int
+    states_generated: int           # every state a walk stood on, the initial states included
+    action_taken: dict              # steps taken per disjunct of Next
+    ended_early: int                # walks that ended on a state without successors
+    longest_walk: int
+    verdict: str                    # "ok" / "invariant" / "deadlock"
+    violated_invariant: Optional[str]
+    violation_walk: int
+    violation_step: int
+    violation_count: dict
+    launches: int
+    seconds_total: float
+    seconds_kernel: float
+
+
+def sim_draw(seed: int, walk: int, step: int, n: int) -> int:
+    """The draw of random simulation (include/kmc.h, kmc_sim_draw): pure, needs no handle."""
+    return int(nat.lib().kmc_sim_draw(seed, walk, step, n))
+
+
 def precompile(cfg: CheckerConfig, arch: str = "gfx950", mode: int = -1) -> None:
     """Specialise + cache the kernels for cfg; needs the HIP compiler but no GPU.  mode: -1 all three code objects of the
     configuration, 0 the search's own, 1 k_expand for the level-step interface, 2 k_expand as an enumerator (include/kmc.h)."""
     c = cfg.to_native()
     nat.check(nat.lib().kmc_precompile_mode(C.byref(c), arch.encode(), mode))
+
+
+def precompile_simulate(cfg: CheckerConfig, arch: str = "gfx950") -> None:
+    """... and k_simulate, the fourth code object: random simulation (ModelChecker.simulate) of cfg's constants."""
+    c = cfg.to_native()
+    nat.check(nat.lib().kmc_precompile_simulate(C.byref(c), arch.encode()))
 
 
 def compiler_identity(which: int = 0) -> int:
@@ -207,6 +235,46 @@ class ModelChecker:
         cb = self._callback(progress)
         nat.check(self._lib.kmc_run(self._h, cb, None))
         return self.result()
+
+    # -- random simulation (TLC -simulate analogue: include/kmc.h holds the contract of a walk) ---------------
+    @staticmethod
+    def _sim_config(seed, n_walks, depth, first_walk, walks_per_launch, record):
+        return nat.KmcSimConfig(seed=seed, first_walk=first_walk, n_walks=n_walks, depth=depth,
+                                walks_per_launch=walks_per_launch, record=int(record))
+
+    def simulate(self, n_walks: int, depth: int = 100, seed: int = 0, first_walk: int = 0, walks_per_launch: int = 0,
+                 record: bool = False) -> SimulateResult:
+        """n_walks random walks of at most `depth` states from Init; walk w is a pure function of (constants, seed, w)."""
+        sc = self._sim_config(seed, n_walks, depth, first_walk, walks_per_launch, record)
+        r = nat.KmcSimResult()
+        nat.check(self._lib.kmc_simulate(self._h, C.byref(sc), C.byref(r)))
+        names = self.action_names()
+        inv_names = nat.invariant_names(self.cfg.model)
+        return SimulateResult(
+            walks=int(r.walks), states_generated=int(r.states_generated),
+            action_taken={names[k]: int(r.action_taken[k]) for k in range(len(names))},
+            ended_early=int(r.ended_early), longest_walk=int(r.longest_walk), verdict=nat.VERDICTS[r.verdict],
+            violated_invariant=(inv_names[r.violated_invariant] if r.violated_invariant >= 0 else None),
+            violation_walk=int(r.violation_walk), violation_step=int(r.violation_step),
+            violation_count={inv_names[k]: int(r.violation_count[k]) for k in range(4) if inv_names[k] != "?"},
+            launches=int(r.launches), seconds_total=float(r.seconds_total), seconds_kernel=float(r.seconds_kernel))
+
+    def walk(self, w: int, depth: int = 100, seed: int = 0) -> list:
+        """[(action name or None, canonical state bytes, choice, n_enabled)] of walk w: read from the last recorded batch
+        when it holds the walk (same seed and depth), else that one walker is run again."""
+        sc = self._sim_config(seed, 1, depth, w, 0, False)
+        cap = depth if depth else 100
+        states = (C.c_uint8 * (cap * self.canon_bytes))()
+        kinds = (C.c_int32 * cap)()
+        choice = (C.c_uint32 * cap)()
+        n_en = (C.c_uint32 * cap)()
+        n = C.c_uint64()
+        nat.check(self._lib.kmc_simulate_walk(self._h, C.byref(sc), w, states, kinds, choice, n_en, cap, C.byref(n)))
+        names = self.action_names()
+        raw = bytes(states)
+        cb = self.canon_bytes
+        return [(None if kinds[i] < 0 else names[kinds[i]], raw[i * cb:(i + 1) * cb], int(choice[i]), int(n_en[i]))
+                for i in range(min(n.value, cap))]
 
     # -- checkpoint / recover (TLC -checkpoint / -recover) ----------------------------------------
     def save_checkpoint(self, path: str) -> None:

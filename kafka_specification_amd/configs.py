@@ -190,6 +190,23 @@ def symmetry_variants():
              for (N, L, K) in SYMMETRY_FRL])
 
 
+def simulate_precompile_list():
+    """(config, environment) pairs whose k_simulate (random simulation: the fourth code object, kmc_precompile_simulate) `build()`
+    specialises: what tests/test_gpu_simulate.py walks, what tools/sim_bench.py measures (the headline, which is also
+    models/Kip320.cfg, and BASELINE config 5).  The search's three objects of these configurations are precompile_list()'s and
+    layout_variants()'."""
+    def k(model, N, L, R, E):
+        return dict(model=model, n_replicas=N, log_size=L, max_records=R, max_leader_epoch=E)
+    small = k("Kip320", 3, 2, 2, 1)
+    return [(small, {}), (small, {"KMC_LAYOUT": "tight"}), (small, {"KMC_LAYOUT": "rm"}),
+            (k("Kip279", 3, 2, 2, 2), {}), (k("KafkaTruncateToHighWatermark", 3, 2, 2, 2), {}), (k("Kip320FirstTry", 3, 2, 2, 2), {}),
+            (k("Kip101", 3, 2, 2, 2), {}), (k("Kip320", 4, 2, 2, 1), {}), (k("Kip320", 7, 1, 1, 0), {}),
+            (dict(model="FiniteReplicatedLog", n_replicas=2, log_size=4, n_log_records=2), {}),
+            (dict(model="IdSequence", max_id=10), {}),
+            ({kk: v for kk, v in HEADLINE.items() if kk != "invariants"}, {}),
+            ({kk: v for kk, v in BASELINE_CONFIGS["config4_kip320_7brokers_log8"].items() if kk != "invariants"}, {})]
+
+
 def layout_variants():
     def c(t):
         return dict(model=t[0], n_replicas=t[1], log_size=t[2], max_records=t[3], max_leader_epoch=t[4])

@@ -3,7 +3,10 @@
 // library (kmc_frontend.cpp), as kafka_specification_amd/tlc.py asks it.
 //
 //   tlc [-config X.cfg] [-deadlock] [-continue] [-workers N] [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-table SLOTS]
-//       [-frontier STATES] [-device D] [-notrace] [-v] Spec.tla
+//       [-frontier STATES] [-device D] [-notrace] [-v] [-walks N [-walk-depth D] [-walk-seed S]] Spec.tla
+//
+// -walks N runs N random walks from Init instead of the search (random simulation: kmc_simulate; stock TLC's -simulate / -depth /
+// -seed spellings stay refused), -walk-depth the states per walk at the most (100), -walk-seed the seed (0).
 //
 // [TLC-recall] flag names and output lines follow tlc2.TLC; TLC itself is not part of the
 // reference repository.  The module name selects one of the lowered models; constants
@@ -43,6 +46,49 @@ void print_state(const kmc_config& c, const uint8_t* b, uint64_t n) {
     printf("%s\n", text.data());
 }
 
+// -walks: a batch of random walks instead of the search; the report's lines are the library's (kmc_sim_report)
+int run_walks(const kmc_config& c, const kmc_sim_config& sim, const std::string& module) {
+    char text[4096];
+    std::vector<const char*> names;
+    for (int k = 0; k < kmc_action_count(c.model); ++k) names.push_back(kmc_action_name(c.model, k));
+    kmc_sim_report(&c, &sim, nullptr, 0, names.data(), (int32_t)names.size(), text, sizeof text);
+    printf("%s\n", text);
+    kmc_handle* h = nullptr;
+    if (kmc_open(&c, &h) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); return 3; }
+    kmc_sim_result r;
+    if (kmc_simulate(h, &sim, &r) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); kmc_close(h); return 3; }
+    int rc = 0;
+    if (r.verdict == KMC_V_OK) {
+        printf("Random simulation completed. No error has been found.\n");
+    } else {
+        if (r.verdict == KMC_V_INVARIANT) printf("Error: Invariant %s is violated%s.\n", kmc_model_invariant_name(c.model, r.violated_invariant),
+                                                 r.violation_step == 0 ? " by the initial state" : "");
+        else printf("Error: Deadlock reached.\n");
+        rc = r.verdict == KMC_V_INVARIANT ? 12 : 11;
+        const uint64_t cb = kmc_canon_bytes(h), cap = r.violation_step + 1;
+        std::vector<uint8_t> states(cap * cb);
+        std::vector<int32_t> kinds(cap);
+        uint64_t nt = 0;
+        if (kmc_simulate_walk(h, &sim, r.violation_walk, states.data(), kinds.data(), nullptr, nullptr, cap, &nt) == KMC_OK) {
+            printf("Error: The behavior up to this point is (walk %llu):\n", (unsigned long long)r.violation_walk);
+            for (uint64_t k = 0; k < nt && k < cap; ++k) {
+                if (k == 0) printf("State 1: <Initial predicate>\n");
+                else printf("State %llu: <%s of module %s>\n", (unsigned long long)(k + 1), kmc_action_name(c.model, kinds[k]), module.c_str());
+                print_state(c, states.data() + k * cb, cb);
+                printf("\n");
+            }
+        } else {
+            fprintf(stderr, "Error: %s\n", kmc_last_error());
+        }
+    }
+    kmc_sim_report(&c, &sim, &r, 1, names.data(), (int32_t)names.size(), text, sizeof text);
+    printf("%s\n", text);
+    printf("Finished in %.3fs (%.0f steps/s in the simulate kernel, %.3fs) at (%s)\n", r.seconds_total,
+           (double)(r.states_generated - r.walks) / (r.seconds_kernel > 1e-9 ? r.seconds_kernel : 1e-9), r.seconds_kernel, now().c_str());
+    kmc_close(h);
+    return rc;
+}
+
 void on_level(const kmc_level_info* i, void*) {
     if (i->depth == 1)
         printf("Finished computing initial states: %llu distinct state generated at %s.\n",
@@ -63,6 +109,7 @@ int main(int argc, char** argv) {
     c.keep_trace = 1;
     bool no_deadlock = false, fpcheck = false, force = false, verbose = false;
     std::string levels_csv;
+    const char *walks = nullptr, *walk_depth = nullptr, *walk_seed = nullptr;
     const double t_main0 = wall_s();
     int32_t stock = KMC_SWITCH_NONE;
     for (int i = 1; i < argc; ++i) {
@@ -89,10 +136,17 @@ int main(int argc, char** argv) {
         else if (a == "-symmetry") c.symmetry = 1;  // orbit counting: one stored state per orbit of the permutations of Replicas
         else if (a == "-force") force = true;
         else if (a == "-levels-csv") levels_csv = val("-levels-csv");  // one line per BFS level: frontier, generated per disjunct, new, table load, kernel ms
+        else if (a == "-walks") walks = val("-walks");   // random simulation: this many walks from Init instead of the search
+        else if (a == "-walk-depth") walk_depth = val("-walk-depth");
+        else if (a == "-walk-seed") walk_seed = val("-walk-seed");
         else if (a == "-v") verbose = true;   // where the wall time went: start-up (HIP, code object, allocation, first touch), search, teardown
         else if (a == "-verify") setenv("KMC_VERIFY", "1", 1);  // every level is regenerated by a second build of the kernels
         else if (const char* why = kmc_tlc_switch(a.c_str(), &stock)) {   // stock TLC's other switches [TLC-recall]
-            if (stock == KMC_SWITCH_REFUSED) { fprintf(stderr, "Error: %s is not supported: %s\n", a.c_str(), why); return 2; }
+            if (stock == KMC_SWITCH_REFUSED) {
+                fprintf(stderr, "Error: %s is not supported: %s\n", a.c_str(), why);
+                if (a == "-simulate") fprintf(stderr, "Note: -walks N [-walk-depth D] [-walk-seed S] runs N random walks from Init\n");
+                return 2;
+            }
             if (stock == KMC_SWITCH_IGNORED) fprintf(stderr, "Note: %s is accepted for compatibility and ignored (%s)\n", a.c_str(), why);
             else fprintf(stderr, "Note: %s %s is accepted for compatibility and ignored (%s)\n", a.c_str(), val(a.c_str()), why);
         } else if (a == "-checkpoint") {
@@ -103,6 +157,9 @@ int main(int argc, char** argv) {
         else if (!a.empty() && a[0] == '-') { fprintf(stderr, "Error: unknown option %s\n", a.c_str()); return 2; }
         else spec = a;
     }
+    kmc_sim_config sim;
+    int32_t walk_mode = 0;
+    if (kmc_walk_switches(walks, walk_depth, walk_seed, &sim, &walk_mode) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); return 2; }
     if (spec.empty()) { fprintf(stderr, "usage: tlc [-config X.cfg] [-deadlock] [-continue] [-fp N] Spec.tla\n"); return 2; }
     size_t slash = spec.find_last_of('/');
     std::string module = spec.substr(slash == std::string::npos ? 0 : slash + 1);
@@ -135,6 +192,7 @@ int main(int argc, char** argv) {
     }
 
     printf("kafka_specification_amd model checker (MI355X, native CLI) — module %s, config %s\n", module.c_str(), cfg_path.c_str());
+    if (walk_mode) return run_walks(c, sim, module);
     printf("Running breadth-first search Model-Checking with fp seed %llu on GPU %d.\n", (unsigned long long)c.hash_seed, c.device);
     printf("Computing initial states...\n");
     kmc_handle* h = nullptr;

@@ -208,11 +208,13 @@ static long expand_vgpr_spills(const std::vector<char>& code, const std::string&
 // `mode` = which k_expand the object holds (kmc_kernels.h, KMC_ONLY_MODE): KMC_MODE_LOCAL — the search's own kernel with the
 // small kernels around it — KMC_MODE_SHARDED or KMC_MODE_ENUM; one cached file each, so that a front end which never steps or
 // enumerates never pays for those kernels, and the search's kernel is not recompiled (minutes at seven brokers) for them.
-extern const char* const MODE_SUFFIX[3] = {"", "_sh", "_en"};
-extern const char* const MODE_FILE_TAG[3] = {"", "-sharded", "-enum"};
+// (mode 3 = KMC_CODEOBJ_SIM: k_simulate, random simulation — kmc_sim.h)
+extern const char* const MODE_SUFFIX[4] = {"", "_sh", "_en", ""};
+extern const char* const MODE_FILE_TAG[4] = {"", "-sharded", "-enum", "-simulate"};
+extern const char* const MODE_KERNEL[4] = {"kmc_expand", "kmc_expand", "kmc_expand", "kmc_simulate"};
 int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<char>* code, std::string* kname,
                     const char* extra_options, std::string* path_out, unsigned mode, const std::string* jit_defines, int layout_mode) {
-    if (mode > KMC_MODE_ENUM) return fail(KMC_E_ARG, "no code object for mode %u", mode);
+    if (mode > KMC_CODEOBJ_SIM) return fail(KMC_E_ARG, "no code object for mode %u", mode);
     KmcLayout lay;
     std::string name, inst;
     if (!validate(cfg, &lay, &name, &inst, layout_mode))
@@ -265,7 +267,9 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     snprintf(key, sizeof key, "%016llx",
              (unsigned long long)fnv1a(src + "|" + arch + "|" + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) +
                                        "|" + defines_key));
-    const std::string dir = cfg.cache_dir ? std::string(cfg.cache_dir) : default_cache_dir();
+    // (k_simulate's objects live in a sub-directory of their own: the cache's top level holds the search's objects, one k_expand each)
+    const std::string top = cfg.cache_dir ? std::string(cfg.cache_dir) : default_cache_dir();
+    const std::string dir = mode == KMC_CODEOBJ_SIM ? top + "/simulate" : top;
     const long long mine = (long long)compiler_id_mine(), pinned = (long long)compiler_id_pinned();
     auto path_of = [&](long long compiler) {
         return dir + "/" + name + "-" + arch + "-" + key + "-c" + std::to_string(compiler) + MODE_FILE_TAG[mode] + ".hsaco";
@@ -318,17 +322,21 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
         code->resize(n);
         hiprtcGetCode(prog, code->data());
         hiprtcDestroyProgram(&prog);
-        const long spills = expand_vgpr_spills(*code, std::string("kmc_expand") + MODE_SUFFIX[mode] + "_" + name);
+        const long spills = expand_vgpr_spills(*code, std::string(MODE_KERNEL[mode]) + MODE_SUFFIX[mode] + "_" + name);
         if (waves_forced) break;  // an explicit -DKMC_MIN_WAVES (tuning, bug hunts) is taken as given and never cached as default
         // The guard must not pass by accident: an unreadable spill count, or a kernel that still spills at
         // one wave per SIMD, is a failed specialisation — not a kernel to run and cache.
+        const std::string kernel = std::string(MODE_KERNEL[mode]) + MODE_SUFFIX[mode] + "_" + name;
         if (spills < 0)
-            return fail(KMC_E_COMPILE, "cannot read .vgpr_spill_count of kmc_expand%s_%s from the code object's metadata: "
-                                       "the register-budget rule cannot be checked", MODE_SUFFIX[mode], name.c_str());
+            return fail(KMC_E_COMPILE, "cannot read .vgpr_spill_count of %s from the code object's metadata: "
+                                       "the register-budget rule cannot be checked", kernel.c_str());
         if (spills <= KMC_MAX_VGPR_SPILLS) break;
-        if (waves == 1)
-            return fail(KMC_E_COMPILE, "kmc_expand%s_%s spills %ld vector registers even at one wave per SIMD: constants too "
-                                       "wide for this kernel shape", MODE_SUFFIX[mode], name.c_str(), spills);
+        // (k_simulate is not compiled against KMC_MIN_WAVES — it holds no LDS ring whose size fixes the residency, the compiler has
+        // the whole register file of one wave per SIMD — so there is no smaller occupancy target to retry with: the same bound
+        // on spilled vector registers holds, and a kernel beyond it is refused)
+        if (waves == 1 || mode == KMC_CODEOBJ_SIM)
+            return fail(KMC_E_COMPILE, "%s spills %ld vector registers even at one wave per SIMD: constants too "
+                                       "wide for this kernel shape", kernel.c_str(), spills);
         // (these kernels take up to minutes to compile: jump by the size of the overflow, do not crawl)
         // (a near miss at 6 waves gets 5 — 96 registers: the kind-major headline kernel spills 9 at 80 and 2 at 96 and runs
         // equally fast at either, profiles/r03_kind_major.txt)
@@ -338,6 +346,7 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
         waves = next < waves ? next : waves - 1;
     }
     // best-effort cache write (atomic rename)
+    mkdir(top.c_str(), 0755);
     mkdir(dir.c_str(), 0755);
     const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
     if (FILE* f = fopen(tmp.c_str(), "wb")) {

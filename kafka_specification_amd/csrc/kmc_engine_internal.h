@@ -7,6 +7,7 @@
 //   kmc_engine_run.cpp       kmc_run's level loop (chained launches), results, kmc_successors / kmc_check_states, traces
 //   kmc_engine_tuning.cpp    ONLY in libkmc_tuning.so (-DKMC_TUNING=1, as the device's tuning build): the dry / shadow passes and launch overrides behind the tuning_* hooks
 //   kmc_engine_step.cpp      checkpoint / recover, the level-step interface of one shard
+//   kmc_sim_engine.cpp       random simulation: kmc_simulate / kmc_simulate_walk / kmc_sim_draw over k_simulate (the fourth code object)
 //   kmc_engine_exchange.cpp  the per-level exchange: RCCL bound with dlopen, the plan, one-shot and pipelined levels, logical shards
 // The engine stands in for TLC's ModelChecker + Worker threads [TLC-recall; TLC is not part of /root/reference].  No CPU fallback
 // exists: without a HIP device or compiler every entry point fails with KMC_E_DEVICE / KMC_E_COMPILE.
@@ -104,6 +105,16 @@ struct kmc_handle {
     hipFunction_t f_expand = nullptr, f_inv = nullptr, f_insert = nullptr, f_init = nullptr, f_find = nullptr, f_packrow = nullptr;
     hipModule_t mod_sh = nullptr, mod_en = nullptr;   // k_expand in SHARDED / ENUM mode: loaded when first needed (ensure_mode)
     hipFunction_t f_expand_sh = nullptr, f_expand_en = nullptr;
+    // random simulation (kmc_sim_engine.cpp): k_simulate's code object, its control block, and the last recorded batch
+    hipModule_t mod_sim = nullptr;
+    hipFunction_t f_sim = nullptr;
+    KmcSimCtl* sim_ctl = nullptr;            // device
+    KmcSimCtl* sim_ctl_host = nullptr;       // pinned
+    u64* sim_rec = nullptr;                  // device: record planes [step][word][column], then the walks' lengths per column
+    uint64_t sim_rec_words = 0;              // allocated
+    struct { uint64_t seed = 0, first_walk = 0, walks_done = 0, stride = 0; uint32_t depth = 0; bool valid = false; } sim_batch;
+    u64* sim_one = nullptr;                  // device: the same for one walker (kmc_simulate_walk's re-run)
+    uint64_t sim_one_words = 0;
     hipModule_t mod_verify = nullptr;       // KMC_VERIFY=1: a second, differently compiled code object whose dry k_expand regenerates every level
     hipFunction_t f_expand_verify = nullptr;
     uint64_t verify_levels = 0;
@@ -189,8 +200,9 @@ extern const char* const KINDS_BASE[9];
 extern const char* const KINDS_KIP320[9];
 extern const char* const KINDS_FIRST[10];
 extern const char* const KINDS_FRL[3];
-extern const char* const MODE_SUFFIX[3];
-extern const char* const MODE_FILE_TAG[3];
+extern const char* const MODE_SUFFIX[4];
+extern const char* const MODE_FILE_TAG[4];
+extern const char* const MODE_KERNEL[4];
 int64_t compiler_id_mine();
 int64_t compiler_id_pinned();
 bool validate(const kmc_config& c, KmcLayout* lay, std::string* name, std::string* inst, int layout_mode = -2);
@@ -243,6 +255,9 @@ void range_pop();
 
 // ---- kmc_engine_exchange.cpp ----
 void comm_release(kmc_handle* h);
+
+// ---- kmc_sim_engine.cpp ----
+void sim_release(kmc_handle* h);   // at kmc_close: the record buffers, the control block, the code object
 
 // ---- kmc_engine_tuning.cpp: what the product's code calls of the tuning aids; no-ops in libkmc.so ----
 #if KMC_TUNING

@@ -40,9 +40,11 @@ const char* kmc_action_name(int32_t model, int32_t kind) {
 
 // mode: 0 the search's own code object (k_expand LOCAL + the small kernels), 1 k_expand SHARDED (the level-step interface),
 // 2 k_expand ENUM (kmc_successors, trace replay); -1 all three.  A build script spreads the modes over its workers.
+// (k_simulate, the fourth object, is kmc_precompile_simulate's: random simulation is asked for by name.)
 int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode) {
     if (!cfg) return fail(KMC_E_ARG, "null config");
-    if (mode < -1 || mode > (int32_t)KMC_MODE_ENUM) return fail(KMC_E_ARG, "mode %d: expected -1 (all), 0 (search), 1 (sharded), 2 (enum)", mode);
+    if (mode < -1 || mode > (int32_t)KMC_MODE_ENUM)
+        return fail(KMC_E_ARG, "mode %d: expected -1 (all), 0 (search), 1 (sharded), 2 (enum); k_simulate is kmc_precompile_simulate's", mode);
     std::vector<char> code;
     std::string kname;
     const bool verify = env_flag("KMC_VERIFY");
@@ -54,6 +56,13 @@ int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode) {
     // with KMC_VERIFY set: also the second build kmc_open would load for the differential self-check
     if (verify && mode <= 0) return get_code_object(*cfg, arch ? arch : "gfx950", &code, &kname, KMC_VERIFY_OPTIONS);
     return KMC_OK;
+}
+int kmc_precompile_simulate(const kmc_config* cfg, const char* arch) {
+    if (!cfg) return fail(KMC_E_ARG, "null config");
+    if (cfg->model == KMC_ASYNC_ISR || cfg->symmetry) return fail(KMC_E_ARG, "random simulation is not for AsyncIsr or symmetry handles");
+    std::vector<char> code;
+    std::string kname;
+    return get_code_object(*cfg, arch ? arch : "gfx950", &code, &kname, nullptr, nullptr, KMC_CODEOBJ_SIM);
 }
 int kmc_precompile(const kmc_config* cfg, const char* arch) { return kmc_precompile_mode(cfg, arch, -1); }
 
@@ -112,6 +121,7 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
     for (hipEvent_t e : h->ev_aux)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
+    sim_release(h);
     if (h->mod_verify) (void)hipModuleUnload(h->mod_verify);
     if (h->mod_sh) (void)hipModuleUnload(h->mod_sh);
     if (h->mod_en) (void)hipModuleUnload(h->mod_en);

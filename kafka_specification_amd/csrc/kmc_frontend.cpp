@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cerrno>
 #include <cstring>
 #include <map>
 #include <set>
@@ -626,6 +627,62 @@ int kmc_collision_report(uint64_t distinct, uint64_t generated, uint64_t orbit_r
     }
     copy_out(s, out, cap);
     return rc;
+}
+
+// The switches of random simulation, for both command lines: -walks N [-walk-depth D] [-walk-seed S], each given as the text
+// that followed it (NULL: the switch was not given).  Stock TLC's -simulate / -depth / -seed stay refused (TLC_SWITCHES).
+static bool whole_number(const char* t, uint64_t* v) {
+    if (!t || !*t) return false;
+    for (const char* q = t; *q; ++q)
+        if (*q < '0' || *q > '9') return false;
+    errno = 0;
+    *v = strtoull(t, nullptr, 10);
+    return errno == 0;
+}
+int kmc_walk_switches(const char* walks, const char* depth, const char* seed, kmc_sim_config* out, int32_t* asked) {
+    if (!out || !asked) return fail(KMC_E_ARG, "kmc_walk_switches: null argument");
+    *asked = walks != nullptr;
+    if (!walks) {
+        if (depth) return fail(KMC_E_ARG, "-walk-depth belongs to -walks N: say how many random walks to run");
+        if (seed) return fail(KMC_E_ARG, "-walk-seed belongs to -walks N: say how many random walks to run");
+        return KMC_OK;
+    }
+    uint64_t n = 0, d = 100, sd = 0;
+    if (!whole_number(walks, &n)) return fail(KMC_E_ARG, "-walks needs a whole number of walks, not '%s'", walks);
+    if (n == 0) return fail(KMC_E_ARG, "-walks 0: a batch holds at least 1 walk");
+    if (depth && (!whole_number(depth, &d) || d == 0 || d > (1u << 20)))
+        return fail(KMC_E_ARG, "-walk-depth needs a number of states between 1 and %u, not '%s'", 1u << 20, depth);
+    if (seed && !whole_number(seed, &sd)) return fail(KMC_E_ARG, "-walk-seed needs a whole number below 2^64, not '%s'", seed);
+    memset(out, 0, sizeof *out);
+    out->n_walks = n;
+    out->depth = (uint32_t)d;
+    out->seed = sd;
+    return KMC_OK;
+}
+
+// What both command lines print around a batch of walks: closing = 0 the opening line, 1 the lines after it (the verdict and
+// the behaviour are the caller's, as for a search; so are the names of the model's actions: this unit stands alone).  Lines joined by '\n'; returns the length of the whole text.
+int64_t kmc_sim_report(const kmc_config* cfg, const kmc_sim_config* sim, const kmc_sim_result* res, int32_t closing,
+                       const char* const* action_names, int32_t n_actions, char* out, uint64_t cap) {
+    if (!cfg || !sim || (closing && !res)) return fail(KMC_E_ARG, "kmc_sim_report: null argument"), -1;
+    std::string s;
+    if (!closing) {
+        s = fmt("Running Random Simulation with seed %llu: %llu walks of at most %u states on GPU %d.", (unsigned long long)sim->seed,
+                (unsigned long long)sim->n_walks, sim->depth ? sim->depth : 100u, cfg->device);
+    } else {
+        s = fmt("Progress: %llu walks run in %llu launches, %llu states checked.\n", (unsigned long long)res->walks,
+                (unsigned long long)res->launches, (unsigned long long)res->states_generated);
+        s += fmt("The number of states generated: %llu\n", (unsigned long long)res->states_generated);
+        s += fmt("Simulation using seed %llu, walks %llu to %llu.\n", (unsigned long long)sim->seed, (unsigned long long)sim->first_walk,
+                 (unsigned long long)(sim->first_walk + res->walks - 1));
+        s += "Steps taken per action:";
+        for (int k = 0; action_names && k < n_actions && k < KMC_MAX_KINDS; ++k)
+            s += fmt(" %s %llu", action_names[k], (unsigned long long)res->action_taken[k]);
+        s += fmt("\n%llu walks ended on a state without successors; the longest walk has %llu states.",
+                 (unsigned long long)res->ended_early, (unsigned long long)res->longest_walk);
+    }
+    copy_out(s, out, cap);
+    return (int64_t)s.size();
 }
 
 int32_t kmc_uncertified_policy(double* advice_above) {

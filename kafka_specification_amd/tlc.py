@@ -2,7 +2,7 @@
 
     python -m kafka_specification_amd.tlc [-config X.cfg] [-deadlock] [-continue] [-workers N]
                                           [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-gpus P] [-table SLOTS]
-                                          [-frontier STATES] Spec.tla
+                                          [-frontier STATES] [-walks N [-walk-depth D] [-walk-seed S]] Spec.tla
 
 Maps the root module's name to its lowered GPU model, reads constants / invariants from the
 .cfg (default: Spec.cfg next to the module), runs the exhaustive search on the GPU and prints
@@ -11,6 +11,9 @@ and ignored (the GPU's waves are the workers).  No TLA+ is parsed: only the modu
 hachikuji/kafka-specification that have a Next are known — so the spec file given on the command line (and
 every module it EXTENDS / INSTANCEs, when found beside it) is hashed against the revision the kernels were
 lowered from (spec_revision.py); an edited spec is refused unless -force.
+
+-walks N runs N random walks from Init instead of the search (random simulation, one GPU; -walk-depth D states per walk at
+the most, default 100; -walk-seed S, default 0).  Stock TLC's -simulate / -depth / -seed spellings stay refused.
 
 The seen-set holds 64-bit fingerprints, like TLC's FPSet: two distinct states with one fingerprint lose a state
 silently.  Like TLC, the summary prints the estimated probability of that; -fpcheck runs the search a second
@@ -61,6 +64,48 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
+def _run_walks(cc, sim, module) -> int:
+    """-walks: a batch of random walks instead of the search; the report's lines are the library's (kmc_sim_report)."""
+    native_cfg = cc.to_native()
+
+    n_actions = nat.lib().kmc_action_count(native_cfg.model)
+    names = (C.c_char_p * n_actions)(*[nat.lib().kmc_action_name(native_cfg.model, k) for k in range(n_actions)])
+
+    def report(res, closing):
+        out = C.create_string_buffer(4096)
+        nat.lib().kmc_sim_report(C.byref(native_cfg), C.byref(sim), None if res is None else C.byref(res), closing, names,
+                                 n_actions, out, len(out))
+        return out.value.decode()
+    print(report(None, 0))
+    try:
+        with ModelChecker(cc) as mc:
+            r = nat.KmcSimResult()
+            nat.check(nat.lib().kmc_simulate(mc.handle, C.byref(sim), C.byref(r)))
+            rc = 0
+            if r.verdict == 0:
+                print("Random simulation completed. No error has been found.")
+            else:
+                if r.verdict == 1:
+                    where = " by the initial state" if r.violation_step == 0 else ""
+                    print(f"Error: Invariant {nat.invariant_names(cc.model)[r.violated_invariant]} is violated{where}.")
+                else:
+                    print("Error: Deadlock reached.")
+                rc = 12 if r.verdict == 1 else 11
+                behaviour = mc.walk(int(r.violation_walk), depth=int(sim.depth), seed=int(sim.seed))
+                print(f"Error: The behavior up to this point is (walk {r.violation_walk}):")
+                for k, (act, st, _choice, _n) in enumerate(behaviour, 1):
+                    print(f"State {k}: " + ("<Initial predicate>" if act is None else f"<{act} of module {module}>"))
+                    print(format_state(cc, st))
+                    print()
+            print(report(r, 1))
+            steps = (r.states_generated - r.walks) / max(r.seconds_kernel, 1e-9)
+            print(f"Finished in {r.seconds_total:.3f}s ({steps:.0f} steps/s in the simulate kernel, {r.seconds_kernel:.3f}s) at ({_now()})")
+            return rc
+    except nat.KmcError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 3
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="tlc", add_help=True, prefix_chars="-")
     ap.add_argument("spec")
@@ -100,6 +145,10 @@ def main(argv=None) -> int:
                     help="differential self-check: a second, differently compiled build of the kernels regenerates every "
                          "level and the per-action / deadlock / violation counts must agree (for constants no oracle reaches)")
     ap.add_argument("-force", action="store_true", help="check the built-in lowering although the spec text differs from it")
+    # (text, not numbers: what the three mean and what is wrong with them is the library's kmc_walk_switches, as for the native CLI)
+    ap.add_argument("-walks", default=None, metavar="N", help="random simulation: N random walks from Init instead of the search")
+    ap.add_argument("-walk-depth", dest="walk_depth", default=None, metavar="D", help="states per walk at the most (100)")
+    ap.add_argument("-walk-seed", dest="walk_seed", default=None, metavar="S", help="seed of the walks (0)")
     ap.add_argument("-v", action="store_true", dest="verbose",
                     help="one more closing line: where the wall time outside the search went (HIP start-up, code object, allocation, "
                          "first touch of the seen-set: kmc_timing)")
@@ -121,6 +170,8 @@ def main(argv=None) -> int:
             i += 1
         elif kind.value == nat.KMC_SWITCH_REFUSED:
             print(f"Error: {t} is not supported: {why}", file=sys.stderr)
+            if t == "-simulate":
+                print("Note: -walks N [-walk-depth D] [-walk-seed S] runs N random walks from Init", file=sys.stderr)
             return 2
         elif (t == "-checkpoint" and i + 1 < len(argv) and argv[i + 1].lstrip("-").isdigit()
               and not os.path.isdir(argv[i + 1])):
@@ -134,6 +185,11 @@ def main(argv=None) -> int:
             kept.append(t)
         i += 1
     a = ap.parse_args(kept)
+    sim, walk_mode = nat.KmcSimConfig(), C.c_int32()
+    enc = lambda v: None if v is None else str(v).encode()   # noqa: E731
+    if nat.lib().kmc_walk_switches(enc(a.walks), enc(a.walk_depth), enc(a.walk_seed), C.byref(sim), C.byref(walk_mode)) != 0:
+        print(f"Error: {nat.lib().kmc_last_error().decode()}", file=sys.stderr)
+        return 2
 
     module = os.path.splitext(os.path.basename(a.spec))[0]
     cfg_path = a.config or os.path.splitext(a.spec)[0] + ".cfg"
@@ -181,6 +237,8 @@ def main(argv=None) -> int:
         print("Warning: -force: checking the BUILT-IN lowering, not the text of the spec given", file=sys.stderr)
 
     print(f"kafka_specification_amd model checker (MI355X) — module {module}, config {os.path.basename(cfg_path)}")
+    if walk_mode.value:
+        return _run_walks(cc, sim, module)
     print(f"Running breadth-first search Model-Checking with fp seed {a.fp} on GPU {a.device}.")
     print("Computing initial states...")
 
