@@ -97,7 +97,7 @@ typedef struct kmc_config {
     int32_t shard_id;
     uint64_t table_capacity;    /* fingerprint slots, rounded up to a multiple of 64 (any size: a table can fill the HBM there
                                    is, 288 GB hold 2^34 narrow or 12.9 G wide entries beside the frontiers); 0 = auto from free
-                                   HBM (a power of two) */
+                                   HBM (a power of two).  A handle with kmc_table_growth_enable STARTS from this size */
     uint64_t frontier_capacity; /* states per frontier buffer; 0 = auto */
     uint64_t send_capacity;     /* n_shards>1: records per (destination, sub-buffer) per level; 0 = auto */
     uint64_t hash_seed;         /* results must not depend on it (collisions aside) */
@@ -208,6 +208,9 @@ int kmc_open(const kmc_config* cfg, kmc_handle** out);
 int kmc_precompile(const kmc_config* cfg, const char* arch);
 int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode);
 int kmc_precompile_simulate(const kmc_config* cfg, const char* arch);
+/* The fifth object is model-independent: the kernels that move a seen-set into a larger one (kmc_table_growth_enable, below),
+ * one build for every configuration, cached under <cache>/table/.  No GPU needed. */
+int kmc_precompile_table(const char* arch);
 /* Path of the cached code object cfg's kernels are loaded from (specialised first if absent; no GPU needed).  A profile
  * records a hash of its kernels' machine code, so that a number is quoted only for the code it was measured on. */
 int kmc_code_object_path(const kmc_config* cfg, const char* arch, char* out, uint64_t cap);
@@ -232,6 +235,32 @@ int kmc_timing_get(kmc_handle* h, kmc_timing* out);
 int kmc_checkpoint_save(kmc_handle* h, const char* path);
 int kmc_checkpoint_load(kmc_handle* h, const char* path);
 int kmc_resume(kmc_handle* h, kmc_progress_cb cb, void* user);
+/* Let kmc_run / kmc_resume enlarge the seen-set at level boundaries instead of ending with KMC_V_TABLE_FULL (TLC's FPSet grows
+ * too [TLC-recall]).  Call right after kmc_open, before the handle's first kmc_run or kmc_checkpoint_load (KMC_E_STATE later: frontiers
+ * that kmc_open sized by itself are re-sized here, and a loaded or searched handle's would be lost).  max_slots = 0: as far as free device memory allows.  n_shards == 1 only:
+ * KMC_E_ARG for a host-only handle or a shard, KMC_E_STATE on the kmc_step_* path (and kmc_step_begin refuses a growing handle).
+ * Before a level is expanded the table is enlarged when
+ *   - the stored states exceed half of it: to the smallest multiple of 64 slots >= 4 x stored (load <= 0.25 afterwards), or
+ *   - the next level alone could pass the load limit (0.92), by the bound min(largest fan-out x its size, frontier_capacity)
+ *     on its new states: far enough that it provably cannot;
+ * to the size that satisfies both, and never by less than a doubling (what a growth costs is mostly its allocation);
+ * capped by max_slots and by what can be allocated while the old table still exists (when nothing can be had the search
+ * goes on in the table it has and ends as it would without growth).  A level is never interrupted and never re-run.
+ * Afterwards kmc_result.table_capacity, kmc_contains, kmc_pred_of, kmc_trace and kmc_checkpoint_save follow the new table; a
+ * checkpoint is loaded into a handle opened with the table_capacity it was saved at.  A rehash that does not carry over exactly
+ * the stored states ends the run with KMC_E_DEVICE.  KMC_REHASH=window|scatter (read here) chooses the kernel: README. */
+int kmc_table_growth_enable(kmc_handle* h, uint64_t max_slots);
+typedef struct kmc_growth_stat {
+    uint64_t depth;        /* the level boundary (depth of the last completed level) */
+    uint64_t old_slots, new_slots;
+    uint64_t moved;        /* entries carried over = stored states at that moment */
+    uint64_t overflow;     /* of those: placed by the second phase (global compare-and-swap behind the LDS windows) */
+    int32_t  kernel;       /* 0 windowed, 1 scatter */
+    int32_t  pad_;
+    double   rehash_ms;    /* HIP events on the engine stream, both phases */
+} kmc_growth_stat;
+/* One record per growth of the last run: fills up to cap entries, returns their number. */
+uint64_t kmc_table_growth_stats(kmc_handle* h, kmc_growth_stat* out, uint64_t cap);
 /* Per-level sizes of the last run: fills up to cap entries, returns the number of levels. */
 uint64_t kmc_level_sizes(kmc_handle* h, uint64_t* out, uint64_t cap);
 /* Per-expansion records of the last run (see kmc_level_stat): fills up to cap entries, returns their number. */
@@ -471,6 +500,12 @@ int32_t kmc_uncertified_policy(double* advice_above);   /* the two numbers above
  * depth / seed of *out filled when -walks was given; KMC_E_ARG with the reason in kmc_last_error() for -walks 0, a value that is
  * no whole number, or -walk-depth / -walk-seed without -walks. */
 int kmc_walk_switches(const char* walks, const char* depth, const char* seed, kmc_sim_config* out, int32_t* asked);
+/* -grow [max_slots], for both command lines: `value` is the text that followed the switch when it is a number (NULL: none).
+ * *max_slots is what kmc_table_growth_enable takes; a run without -table starts from KMC_GROW_START_SLOTS. */
+#define KMC_GROW_START_SLOTS (1ull << 24)
+int kmc_grow_switch(const char* value, uint64_t* table_capacity, uint64_t* max_slots);
+/* the line -v prints per growth; returns its length */
+int64_t kmc_growth_report(const kmc_growth_stat* g, char* out, uint64_t cap);
 /* What both command lines print around a batch: closing = 0 the opening line (res may be NULL), 1 the lines after the batch,
  * action_names[0 .. n_actions-1] (kmc_action_name) heading the per-action step counts.  Lines joined by '\n'; returns the
  * length of the whole text, -1 on a null argument. */

@@ -89,6 +89,11 @@ class KmcLevelStat(C.Structure):
                 ("table_load", C.c_double), ("expand_ms", C.c_double)]
 
 
+class KmcGrowthStat(C.Structure):
+    _fields_ = [("depth", C.c_uint64), ("old_slots", C.c_uint64), ("new_slots", C.c_uint64), ("moved", C.c_uint64),
+                ("overflow", C.c_uint64), ("kernel", C.c_int32), ("pad_", C.c_int32), ("rehash_ms", C.c_double)]
+
+
 class KmcSimConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_walk", C.c_uint64), ("n_walks", C.c_uint64), ("depth", C.c_uint32),
                 ("walks_per_launch", C.c_uint32), ("record", C.c_int32), ("pad_", C.c_int32)]
@@ -111,6 +116,9 @@ SYMBOLS = [
     ("kmc_precompile", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
     ("kmc_precompile_mode", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_int32]),
     ("kmc_precompile_simulate", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
+    ("kmc_precompile_table", C.c_int, [C.c_char_p]),
+    ("kmc_table_growth_enable", C.c_int, [_H, C.c_uint64]),
+    ("kmc_table_growth_stats", C.c_uint64, [_H, C.POINTER(KmcGrowthStat), C.c_uint64]),
     ("kmc_code_object_path", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_char_p, C.c_uint64]),
     ("kmc_run", C.c_int, [_H, PROGRESS_CB, C.c_void_p]),
     ("kmc_result_get", C.c_int, [_H, C.POINTER(KmcResult)]),
@@ -179,6 +187,8 @@ SYMBOLS = [
     ("kmc_collision_report", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
     ("kmc_uncertified_policy", C.c_int32, [C.POINTER(C.c_double)]),
     ("kmc_walk_switches", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(KmcSimConfig), C.POINTER(C.c_int32)]),
+    ("kmc_grow_switch", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("kmc_growth_report", C.c_int64, [C.POINTER(KmcGrowthStat), C.c_char_p, C.c_uint64]),
     ("kmc_sim_report", C.c_int64, [C.POINTER(KmcConfig), C.POINTER(KmcSimConfig), C.POINTER(KmcSimResult), C.c_int32,
                                    C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_uint64]),
 ]

@@ -131,6 +131,11 @@ def precompile_simulate(cfg: CheckerConfig, arch: str = "gfx950") -> None:
     nat.check(nat.lib().kmc_precompile_simulate(C.byref(c), arch.encode()))
 
 
+def precompile_table(arch: str = "gfx950") -> None:
+    """... and the model-independent fifth: the kernels that move a seen-set into a larger one (ModelChecker.enable_table_growth)."""
+    nat.check(nat.lib().kmc_precompile_table(arch.encode()))
+
+
 def compiler_identity(which: int = 0) -> int:
     """0: the hiprtc / comgr this process compiles with; 1: the pinned one (include/kmc.h, kmc_compiler_identity)."""
     return int(nat.lib().kmc_compiler_identity(which))
@@ -235,6 +240,21 @@ class ModelChecker:
         cb = self._callback(progress)
         nat.check(self._lib.kmc_run(self._h, cb, None))
         return self.result()
+
+    # -- the growing seen-set (include/kmc.h, kmc_table_growth_enable) ----------------------------------------
+    def enable_table_growth(self, max_slots: int = 0) -> None:
+        """run() / resume() enlarge the seen-set at level boundaries instead of ending with table_full; call before run().
+        max_slots = 0: as far as free device memory allows.  One GPU only."""
+        nat.check(self._lib.kmc_table_growth_enable(self._h, max_slots))
+
+    def growth_stats(self) -> list:
+        """One dict per growth of the last run (kmc_growth_stat)."""
+        n = int(self._lib.kmc_table_growth_stats(self._h, None, 0))
+        buf = (nat.KmcGrowthStat * max(n, 1))()
+        n = min(n, int(self._lib.kmc_table_growth_stats(self._h, buf, n)))
+        return [dict(depth=int(b.depth), old_slots=int(b.old_slots), new_slots=int(b.new_slots), moved=int(b.moved),
+                     overflow=int(b.overflow), kernel=("window", "scatter")[b.kernel], rehash_ms=float(b.rehash_ms))
+                for b in buf[:n]]
 
     # -- random simulation (TLC -simulate analogue: include/kmc.h holds the contract of a walk) ---------------
     @staticmethod

@@ -2,7 +2,7 @@
 // handling, the run and its TLC-shaped report.  What a .cfg, a spec file, a state and a stock-TLC switch mean is asked of the
 // library (kmc_frontend.cpp), as kafka_specification_amd/tlc.py asks it.
 //
-//   tlc [-config X.cfg] [-deadlock] [-continue] [-workers N] [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-table SLOTS]
+//   tlc [-config X.cfg] [-deadlock] [-continue] [-workers N] [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-table SLOTS] [-grow [MAX_SLOTS]]
 //       [-frontier STATES] [-device D] [-notrace] [-v] [-walks N [-walk-depth D] [-walk-seed S]] Spec.tla
 //
 // -walks N runs N random walks from Init instead of the search (random simulation: kmc_simulate; stock TLC's -simulate / -depth /
@@ -110,6 +110,8 @@ int main(int argc, char** argv) {
     bool no_deadlock = false, fpcheck = false, force = false, verbose = false;
     std::string levels_csv;
     const char *walks = nullptr, *walk_depth = nullptr, *walk_seed = nullptr;
+    bool grow = false;
+    const char* grow_max = nullptr;
     const double t_main0 = wall_s();
     int32_t stock = KMC_SWITCH_NONE;
     for (int i = 1; i < argc; ++i) {
@@ -136,6 +138,10 @@ int main(int argc, char** argv) {
         else if (a == "-symmetry") c.symmetry = 1;  // orbit counting: one stored state per orbit of the permutations of Replicas
         else if (a == "-force") force = true;
         else if (a == "-levels-csv") levels_csv = val("-levels-csv");  // one line per BFS level: frontier, generated per disjunct, new, table load, kernel ms
+        else if (a == "-grow") {   // the seen-set grows during the search; an optional limit in slots follows
+            grow = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') grow_max = argv[++i];
+        }
         else if (a == "-walks") walks = val("-walks");   // random simulation: this many walks from Init instead of the search
         else if (a == "-walk-depth") walk_depth = val("-walk-depth");
         else if (a == "-walk-seed") walk_seed = val("-walk-seed");
@@ -160,6 +166,8 @@ int main(int argc, char** argv) {
     kmc_sim_config sim;
     int32_t walk_mode = 0;
     if (kmc_walk_switches(walks, walk_depth, walk_seed, &sim, &walk_mode) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); return 2; }
+    uint64_t grow_max_slots = 0;
+    if (grow && kmc_grow_switch(grow_max, &c.table_capacity, &grow_max_slots) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); return 2; }
     if (spec.empty()) { fprintf(stderr, "usage: tlc [-config X.cfg] [-deadlock] [-continue] [-fp N] Spec.tla\n"); return 2; }
     size_t slash = spec.find_last_of('/');
     std::string module = spec.substr(slash == std::string::npos ? 0 : slash + 1);
@@ -198,6 +206,7 @@ int main(int argc, char** argv) {
     kmc_handle* h = nullptr;
     const double t_open0 = wall_s();
     if (kmc_open(&c, &h) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); return 3; }
+    if (grow && kmc_table_growth_enable(h, grow_max_slots) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); kmc_close(h); return 3; }
     const double t_run0 = wall_s();
     if (kmc_run(h, on_level, nullptr) != KMC_OK) { fprintf(stderr, "Error: %s\n", kmc_last_error()); kmc_close(h); return 3; }
     const double t_run1 = wall_s();
@@ -206,6 +215,14 @@ int main(int argc, char** argv) {
     kmc_timing tm;
     memset(&tm, 0, sizeof tm);
     kmc_timing_get(h, &tm);
+    if (verbose) {
+        std::vector<kmc_growth_stat> gs(kmc_table_growth_stats(h, nullptr, 0));
+        kmc_table_growth_stats(h, gs.data(), gs.size());
+        for (const kmc_growth_stat& g : gs) {
+            char line[512];
+            if (kmc_growth_report(&g, line, sizeof line) >= 0) printf("%s\n", line);
+        }
+    }
     int rc = 0;
     if (r.verdict == KMC_V_OK) {
         printf("Model checking completed. No error has been found.\n");

@@ -204,6 +204,64 @@ static long expand_vgpr_spills(const std::vector<char>& code, const std::string&
     return -1;
 }
 
+// ---- what every cached code object shares: its key, its file, one hiprtc compile ----------------------------------------------
+// the key: source text, architecture, hiprtc version, defines
+static std::string cache_key(const std::string& src, const std::string& arch, const std::string& defines_key) {
+    int rtc_major = 0, rtc_minor = 0;
+    hiprtcVersion(&rtc_major, &rtc_minor);
+    char key[64];
+    snprintf(key, sizeof key, "%016llx",
+             (unsigned long long)fnv1a(src + "|" + arch + "|" + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) +
+                                       "|" + defines_key));
+    return key;
+}
+// <dir>/<stem>-<arch>-<key>-c<compiler><tag>.hsaco: the pinned compiler's object when the cache holds it, else this process's own.
+// True: *code holds it.  *path: the file that was read, or the one this process's compile belongs in.
+static bool cache_fetch(const std::string& dir, const std::string& stem, const std::string& arch, const std::string& key,
+                        const char* tag, std::vector<char>* code, std::string* path) {
+    const long long mine = (long long)compiler_id_mine(), pinned = (long long)compiler_id_pinned();
+    auto path_of = [&](long long compiler) { return dir + "/" + stem + "-" + arch + "-" + key + "-c" + std::to_string(compiler) + tag + ".hsaco"; };
+    if (pinned && pinned != mine) {
+        *path = path_of(pinned);
+        if (read_file(*path, code)) return true;
+    }
+    *path = path_of(mine);
+    return read_file(*path, code);
+}
+// best-effort cache write (atomic rename)
+static void cache_store(const std::string& top, const std::string& dir, const std::string& path, const std::vector<char>& code) {
+    mkdir(top.c_str(), 0755);
+    mkdir(dir.c_str(), 0755);
+    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
+    if (FILE* f = fopen(tmp.c_str(), "wb")) {
+        const bool ok = fwrite(code.data(), 1, code.size(), f) == code.size();
+        fclose(f);
+        if (ok) rename(tmp.c_str(), path.c_str());
+        else unlink(tmp.c_str());
+    }
+}
+// one hiprtc compile of `src` under `opts`; `what` names it in the error
+static int compile_text(const std::string& src, const char* file, const std::vector<const char*>& opts, const char* what, std::vector<char>* code) {
+    hiprtcProgram prog;
+    if (hiprtcCreateProgram(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+        return fail(KMC_E_COMPILE, "hiprtcCreateProgram failed");
+    hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), const_cast<const char**>(opts.data()));
+    if (r != HIPRTC_SUCCESS) {
+        size_t ln = 0;
+        hiprtcGetProgramLogSize(prog, &ln);
+        std::string log(ln, 0);
+        if (ln) hiprtcGetProgramLog(prog, &log[0]);
+        hiprtcDestroyProgram(&prog);
+        return fail(KMC_E_COMPILE, "hiprtc failed for %s: %s\n%.1500s", what, hiprtcGetErrorString(r), log.c_str());
+    }
+    size_t n = 0;
+    hiprtcGetCodeSize(prog, &n);
+    code->resize(n);
+    hiprtcGetCode(prog, code->data());
+    hiprtcDestroyProgram(&prog);
+    return KMC_OK;
+}
+
 // Compile (or fetch from the cache) the code object specialised for cfg.
 // `mode` = which k_expand the object holds (kmc_kernels.h, KMC_ONLY_MODE): KMC_MODE_LOCAL — the search's own kernel with the
 // small kernels around it — KMC_MODE_SHARDED or KMC_MODE_ENUM; one cached file each, so that a front end which never steps or
@@ -261,29 +319,15 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     // measured on) when the cache holds it — a gfx950 code object loads under either runtime — so the bench and a profile run
     // still execute the same machine code.  A process bound to another compiler that finds no pinned object compiles its own,
     // under its own name.
-    int rtc_major = 0, rtc_minor = 0;
-    hiprtcVersion(&rtc_major, &rtc_minor);
-    char key[64];
-    snprintf(key, sizeof key, "%016llx",
-             (unsigned long long)fnv1a(src + "|" + arch + "|" + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) +
-                                       "|" + defines_key));
+    const std::string key = cache_key(src, arch, defines_key);
     // (k_simulate's objects live in a sub-directory of their own: the cache's top level holds the search's objects, one k_expand each)
     const std::string top = cfg.cache_dir ? std::string(cfg.cache_dir) : default_cache_dir();
     const std::string dir = mode == KMC_CODEOBJ_SIM ? top + "/simulate" : top;
     const long long mine = (long long)compiler_id_mine(), pinned = (long long)compiler_id_pinned();
-    auto path_of = [&](long long compiler) {
-        return dir + "/" + name + "-" + arch + "-" + key + "-c" + std::to_string(compiler) + MODE_FILE_TAG[mode] + ".hsaco";
-    };
-    if (pinned && pinned != mine) {
-        const std::string pp = path_of(pinned);
-        if (read_file(pp, code)) {
-            if (path_out) *path_out = pp;
-            return KMC_OK;
-        }
-    }
-    const std::string path = path_of(mine);
+    std::string path;
+    const bool cached = cache_fetch(dir, name, arch, key, MODE_FILE_TAG[mode], code, &path);
     if (path_out) *path_out = path;
-    if (read_file(path, code)) return KMC_OK;
+    if (cached) return KMC_OK;
     const bool verbose = env_str("KMC_VERBOSE") != nullptr;
     if (verbose && pinned && pinned != mine)
         fprintf(stderr, "[kmc] no code object of the pinned compiler %lld for %s in %s: compiling with this process's (%lld)\n", pinned,
@@ -299,29 +343,14 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     // kernel: recompile with fewer waves per SIMD until k_expand spills (almost) no VGPRs.  An explicit
     // -DKMC_MIN_WAVES in KMC_JIT_DEFINES is respected as given.
     const bool waves_forced = defines_key.find("KMC_MIN_WAVES") != std::string::npos;
-    size_t n = 0;
     for (int waves = 6; waves >= 1;) {
-        hiprtcProgram prog;
-        if (hiprtcCreateProgram(&prog, src.c_str(), "kmc_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-            return fail(KMC_E_COMPILE, "hiprtcCreateProgram failed");
         const std::string archopt = "--offload-arch=" + arch;
         const std::string wavesopt = "-DKMC_MIN_WAVES=" + std::to_string(waves);
         std::vector<const char*> opts = {archopt.c_str(), "-O3", "-std=c++17"};
         if (!waves_forced) opts.push_back(wavesopt.c_str());
         for (const std::string& d : defines) opts.push_back(d.c_str());
-        hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-        if (r != HIPRTC_SUCCESS) {
-            size_t ln = 0;
-            hiprtcGetProgramLogSize(prog, &ln);
-            std::string log(ln, 0);
-            if (ln) hiprtcGetProgramLog(prog, &log[0]);
-            hiprtcDestroyProgram(&prog);
-            return fail(KMC_E_COMPILE, "hiprtc failed for %s: %s\n%.1500s", name.c_str(), hiprtcGetErrorString(r), log.c_str());
-        }
-        hiprtcGetCodeSize(prog, &n);
-        code->resize(n);
-        hiprtcGetCode(prog, code->data());
-        hiprtcDestroyProgram(&prog);
+        const int rc = compile_text(src, "kmc_jit.hip", opts, name.c_str(), code);
+        if (rc) return rc;
         const long spills = expand_vgpr_spills(*code, std::string(MODE_KERNEL[mode]) + MODE_SUFFIX[mode] + "_" + name);
         if (waves_forced) break;  // an explicit -DKMC_MIN_WAVES (tuning, bug hunts) is taken as given and never cached as default
         // The guard must not pass by accident: an unreadable spill count, or a kernel that still spills at
@@ -345,16 +374,25 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
         const int next = spills > 64 ? 2 : spills > 40 ? 3 : spills > 24 ? 4 : 5;
         waves = next < waves ? next : waves - 1;
     }
-    // best-effort cache write (atomic rename)
-    mkdir(top.c_str(), 0755);
-    mkdir(dir.c_str(), 0755);
-    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-    if (FILE* f = fopen(tmp.c_str(), "wb")) {
-        bool ok = fwrite(code->data(), 1, n, f) == n;
-        fclose(f);
-        if (ok) rename(tmp.c_str(), path.c_str());
-        else unlink(tmp.c_str());
-    }
+    cache_store(top, dir, path, *code);
+    return KMC_OK;
+}
+
+// The model-independent code object of the growing seen-set (kmc_rehash.h: k_rehash_window / _overflow / _scatter for every entry
+// shape), cached under <cache>/table/ with the compiler's identity in the file name and the pinned compiler's object preferred,
+// as above.  It is compiled from a text of its own (KMC_SRC_REHASH): no model-specialised object changes with it.
+int get_table_code_object(const char* cache_dir, const std::string& arch, std::vector<char>* code, std::string* path_out) {
+    const std::string src = strip_for_concat(KMC_SRC_REHASH) + "\nKMC_REHASH_INSTANTIATE_ALL\n";
+    const std::string top = cache_dir ? std::string(cache_dir) : default_cache_dir();
+    const std::string dir = top + "/table";
+    std::string path;
+    const bool cached = cache_fetch(dir, "kmc_table", arch, cache_key(src, arch, ""), "", code, &path);
+    if (path_out) *path_out = path;
+    if (cached) return KMC_OK;
+    const std::string archopt = "--offload-arch=" + arch;
+    const int rc = compile_text(src, "kmc_table_jit.hip", {archopt.c_str(), "-O3", "-std=c++17"}, "the table kernels", code);
+    if (rc) return rc;
+    cache_store(top, dir, path, *code);
     return KMC_OK;
 }
 

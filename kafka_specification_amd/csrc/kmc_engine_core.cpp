@@ -355,6 +355,7 @@ int reset_run(kmc_handle* h) {
     HIP_TRY(hipMemsetAsync(h->ctl, 0, KMC_CTL_SLOTS * sizeof(KmcLevelCtl), h->stream));
     h->levels.clear();
     h->level_stats.clear();
+    h->growth.stats.clear();
     h->step_expand_ms = 0;
     h->witness.clear();
     h->have_witness = false;

@@ -8,6 +8,7 @@
 //   kmc_engine_tuning.cpp    ONLY in libkmc_tuning.so (-DKMC_TUNING=1, as the device's tuning build): the dry / shadow passes and launch overrides behind the tuning_* hooks
 //   kmc_engine_step.cpp      checkpoint / recover, the level-step interface of one shard
 //   kmc_sim_engine.cpp       random simulation: kmc_simulate / kmc_simulate_walk / kmc_sim_draw over k_simulate (the fourth code object)
+//   kmc_growth_engine.cpp    the growing seen-set: kmc_table_growth_enable / _stats, when and how far (grow_if_needed), the rehash launches
 //   kmc_engine_exchange.cpp  the per-level exchange: RCCL bound with dlopen, the plan, one-shot and pipelined levels, logical shards
 // The engine stands in for TLC's ModelChecker + Worker threads [TLC-recall; TLC is not part of /root/reference].  No CPU fallback
 // exists: without a HIP device or compiler every entry point fails with KMC_E_DEVICE / KMC_E_COMPILE.
@@ -34,6 +35,7 @@
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-parameter"
 #include "kmc_device.h"   // host-visible parts: KmcArgs, KmcLevelCtl, layout, fingerprint
+#include "kmc_rehash.h"   // ... and of the growing seen-set's code object: KmcRehashArgs, KmcRehashCtl
 #pragma clang diagnostic pop
 
 // Levels kmc_run queues back to back before it waits (no progress callback): see run_levels.
@@ -87,6 +89,19 @@ struct kmc_tuning {   // the tuning aids' part of a handle (kmc_engine_tuning.cp
 };
 #endif
 
+// The growing seen-set of a handle (kmc_table_growth_enable; kmc_growth_engine.cpp)
+struct kmc_growth {
+    bool enabled = false;
+    uint64_t max_slots = 0;                 // 0: as far as free device memory allows
+    int kernel = 0;                         // KMC_REHASH: 0 windowed, 1 scatter
+    uint64_t window_bytes = 32 * 1024;      // KMC_REHASH_WINDOW_KIB: LDS of one window (32 KiB: profiles/table_growth.json)
+    hipModule_t mod = nullptr;              // the table code object (kmc_rehash.h), joined on first use
+    hipFunction_t f_window = nullptr, f_overflow = nullptr, f_scatter = nullptr;
+    KmcRehashCtl* ctl = nullptr;            // device
+    KmcRehashCtl* ctl_host = nullptr;       // pinned
+    std::vector<kmc_growth_stat> stats;     // of the last run
+};
+
 struct kmc_handle {
     kmc_config cfg{};
     KmcLayout lay{};
@@ -98,6 +113,7 @@ struct kmc_handle {
     std::string cache_dir;                  // kmc_config.cache_dir, copied: the later code objects (ensure_mode) are looked up
                                             // long after kmc_open returned and the caller's string may be gone
     kmc_knobs knobs;                        // the environment as it stood when the handle was opened
+    kmc_growth growth;
 #if KMC_TUNING
     kmc_tuning tuning;
 #endif
@@ -214,6 +230,7 @@ inline bool env_flag(const char* name) { return env_int(name, 0) != 0; }
 int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<char>* code, std::string* kname,
                     const char* extra_options = nullptr, std::string* path_out = nullptr, unsigned mode = KMC_MODE_LOCAL,
                     const std::string* jit_defines = nullptr, int layout_mode = -2);
+int get_table_code_object(const char* cache_dir, const std::string& arch, std::vector<char>* code, std::string* path_out = nullptr);
 uint64_t pow2_floor(uint64_t x);
 uint64_t pow2_ceil(uint64_t x);
 double now_s();
@@ -258,6 +275,14 @@ void comm_release(kmc_handle* h);
 
 // ---- kmc_sim_engine.cpp ----
 void sim_release(kmc_handle* h);   // at kmc_close: the record buffers, the control block, the code object
+
+// ---- kmc_engine_open.cpp ----
+uint64_t auto_frontier_capacity(const kmc_handle* h, double budget);
+
+// ---- kmc_growth_engine.cpp ----
+// at a level boundary of run_levels, on a handle with growth enabled: enlarges the seen-set when the load rule or the safety rule asks
+int grow_if_needed(kmc_handle* h);
+void growth_release(kmc_handle* h);   // at kmc_close
 
 // ---- kmc_engine_tuning.cpp: what the product's code calls of the tuning aids; no-ops in libkmc.so ----
 #if KMC_TUNING

@@ -122,6 +122,7 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     sim_release(h);
+    growth_release(h);
     if (h->mod_verify) (void)hipModuleUnload(h->mod_verify);
     if (h->mod_sh) (void)hipModuleUnload(h->mod_sh);
     if (h->mod_en) (void)hipModuleUnload(h->mod_en);
@@ -143,6 +144,16 @@ static void read_knobs(kmc_knobs* k) {
     k->seen_set_spread = spread < 1 ? 1 : spread > 64 ? 64 : spread;
     k->seen_set_chunk_log2 = (int)env_int("KMC_SEEN_SET_CHUNK_LOG2", 23);
 }
+
+namespace kmc_engine {
+// States per frontier buffer when the caller names none: a share of the memory budget, in whole 512-byte-aligned segments.  (kmc_open
+// clips it to the table it allocates; kmc_table_growth_enable, whose table will not stay that small, does not.)
+uint64_t auto_frontier_capacity(const kmc_handle* h, double budget) {
+    const double share = h->cfg.n_shards > 1 ? 0.09 : 0.20;
+    const uint64_t fcap = (uint64_t)(budget * share) / (8ull * h->planes);
+    return (fcap + 64 * KMC_SEGS - 1) / (64 * KMC_SEGS) * (64 * KMC_SEGS);
+}
+}  // namespace kmc_engine
 
 static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     h->cfg = *cfg;
@@ -252,8 +263,7 @@ static int open_impl(const kmc_config* cfg, kmc_handle* h) {
     if (tcap >> 6 > 0xFFFFFFFFull) return fail(KMC_E_ARG, "table_capacity %llu: at most 2^38 slots", (unsigned long long)tcap);
     uint64_t fcap = cfg->frontier_capacity;
     if (!fcap) {
-        const double share = h->cfg.n_shards > 1 ? 0.09 : 0.20;
-        fcap = (uint64_t)(budget * share) / (8ull * h->planes);
+        fcap = auto_frontier_capacity(h, budget);
         if (fcap > tcap) fcap = tcap;
     }
     if (fcap < 64) fcap = 64;

@@ -111,6 +111,9 @@ static int run_levels(kmc_handle* h, kmc_progress_cb cb, void* user, bool fresh)
             r.queue_left = queue_now(h);
             break;
         }
+        // the seen-set of a growing handle is enlarged here, between two levels, and nowhere else: both launch paths below read
+        // h->table / h->table_cap afresh, and the chain's `room` is computed from the new capacity
+        if (h->growth.enabled && (rc = grow_if_needed(h))) return rc;
         // Under -continue a violation does not end the search, so levels queued behind the violating one would run and
         // overwrite its parent frontier before the host could fetch the witness (find_state / find_outside_witness):
         // such runs go level by level until the first violation has been recorded, and chain from there on.

@@ -176,6 +176,7 @@ int kmc_checkpoint_load(kmc_handle* h, const char* path) {
 int kmc_step_begin(kmc_handle* h) {
     if (!h) return fail(KMC_E_ARG, "null handle");
     if (!h->table) return fail(KMC_E_STATE, "host-only handle (device = -1) cannot run");
+    if (h->growth.enabled) return fail(KMC_E_STATE, "a handle with table growth enabled runs through kmc_run / kmc_resume: the level-step interface keeps its table");
     HIP_TRY(hipSetDevice(h->cfg.device));
     int rc = do_begin(h);
     h->stepping = true;

@@ -660,6 +660,27 @@ int kmc_walk_switches(const char* walks, const char* depth, const char* seed, km
     return KMC_OK;
 }
 
+// -grow [max_slots], for both command lines: the seen-set grows during the search (kmc_table_growth_enable).  A run that names
+// no -table starts from KMC_GROW_START_SLOTS instead of half the free HBM: what the switch is for is not having to know a size.
+int kmc_grow_switch(const char* value, uint64_t* table_capacity, uint64_t* max_slots) {
+    if (!table_capacity || !max_slots) return fail(KMC_E_ARG, "kmc_grow_switch: null argument");
+    *max_slots = 0;
+    if (value && !whole_number(value, max_slots)) return fail(KMC_E_ARG, "-grow takes a whole number of slots (or nothing), not '%s'", value);
+    if (*table_capacity == 0) *table_capacity = KMC_GROW_START_SLOTS;
+    if (*max_slots && *max_slots < *table_capacity)
+        return fail(KMC_E_ARG, "-grow %llu: the limit is below the %llu slots the search starts from", (unsigned long long)*max_slots,
+                    (unsigned long long)*table_capacity);
+    return KMC_OK;
+}
+int64_t kmc_growth_report(const kmc_growth_stat* g, char* out, uint64_t cap) {
+    if (!g || !out || !cap) return fail(KMC_E_ARG, "kmc_growth_report: null argument"), -1;
+    const std::string s = fmt("Seen-set grown at depth %llu: %llu -> %llu slots, %llu entries moved (%llu by the second phase), %s kernel, %.3f ms.",
+                              (unsigned long long)g->depth, (unsigned long long)g->old_slots, (unsigned long long)g->new_slots,
+                              (unsigned long long)g->moved, (unsigned long long)g->overflow, g->kernel ? "scatter" : "windowed", g->rehash_ms);
+    snprintf(out, cap, "%s", s.c_str());
+    return (int64_t)s.size();
+}
+
 // What both command lines print around a batch of walks: closing = 0 the opening line, 1 the lines after it (the verdict and
 // the behaviour are the caller's, as for a search; so are the names of the model's actions: this unit stands alone).  Lines joined by '\n'; returns the length of the whole text.
 int64_t kmc_sim_report(const kmc_config* cfg, const kmc_sim_config* sim, const kmc_sim_result* res, int32_t closing,

@@ -1,7 +1,7 @@
 """`tlc2.TLC`-shaped command line [TLC-recall]:
 
     python -m kafka_specification_amd.tlc [-config X.cfg] [-deadlock] [-continue] [-workers N]
-                                          [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-gpus P] [-table SLOTS]
+                                          [-fp SEED] [-fp128] [-symmetry] [-fpcheck] [-verify] [-force] [-levels-csv FILE] [-gpus P] [-table SLOTS] [-grow [MAX_SLOTS]]
                                           [-frontier STATES] [-walks N [-walk-depth D] [-walk-seed S]] Spec.tla
 
 Maps the root module's name to its lowered GPU model, reads constants / invariants from the
@@ -149,6 +149,9 @@ def main(argv=None) -> int:
     ap.add_argument("-walks", default=None, metavar="N", help="random simulation: N random walks from Init instead of the search")
     ap.add_argument("-walk-depth", dest="walk_depth", default=None, metavar="D", help="states per walk at the most (100)")
     ap.add_argument("-walk-seed", dest="walk_seed", default=None, metavar="S", help="seed of the walks (0)")
+    ap.add_argument("-grow", nargs="?", const="", default=None, metavar="MAX_SLOTS",
+                    help="the seen-set grows during the search instead of ending it with table_full (one GPU); without -table the "
+                         "search starts from 2^24 slots; MAX_SLOTS limits the growth (default: the free device memory)")
     ap.add_argument("-v", action="store_true", dest="verbose",
                     help="one more closing line: where the wall time outside the search went (HIP start-up, code object, allocation, "
                          "first touch of the seen-set: kmc_timing)")
@@ -190,6 +193,18 @@ def main(argv=None) -> int:
     if nat.lib().kmc_walk_switches(enc(a.walks), enc(a.walk_depth), enc(a.walk_seed), C.byref(sim), C.byref(walk_mode)) != 0:
         print(f"Error: {nat.lib().kmc_last_error().decode()}", file=sys.stderr)
         return 2
+
+    grow_max = C.c_uint64()
+    if a.grow is not None:
+        if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:   # (as the library refuses n_shards > 1: a shard keeps its table)
+            print("Error: -grow is for one GPU: the shards of -gpus P / torch.distributed.run keep the tables they are opened with",
+                  file=sys.stderr)
+            return 2
+        table = C.c_uint64(a.table)
+        if nat.lib().kmc_grow_switch(enc(a.grow or None), C.byref(table), C.byref(grow_max)) != 0:
+            print(f"Error: {nat.lib().kmc_last_error().decode()}", file=sys.stderr)
+            return 2
+        a.table = table.value
 
     module = os.path.splitext(os.path.basename(a.spec))[0]
     cfg_path = a.config or os.path.splitext(a.spec)[0] + ".cfg"
@@ -261,8 +276,11 @@ def main(argv=None) -> int:
             res = check_loopback(conf, a.gpus, a.device, progress, a.checkpoint, a.recover)
             return res, res.trace   # walked owner by owner through the shards' predecessor tables
         with ModelChecker(conf) as mc:
+            if a.grow is not None:
+                mc.enable_table_growth(grow_max.value)
             res = mc.run(progress)
             timing.update(mc.timing())
+            growths[:] = mc.growth_stats()
             nonlocal level_rows
             level_rows = mc.level_stats()
             trace = []
@@ -274,6 +292,7 @@ def main(argv=None) -> int:
 
     second = None
     timing = {}
+    growths = []
     level_rows = None   # -levels-csv: the per-expansion records of the search on one GPU (kmc_level_stats)
     try:
         res, trace = search(cc, progress)
@@ -333,6 +352,13 @@ def main(argv=None) -> int:
             rc = 13
     print(f"Finished in {res.seconds_total:.3f}s ({res.distinct / max(res.seconds_total, 1e-9):,.0f} distinct states/s; "
           f"{res.seconds_expand:.3f}s in the expand kernel) at ({_now()})")
+    if a.verbose:
+        for g in growths:   # (the line is the library's, as for the native CLI)
+            st = nat.KmcGrowthStat(depth=g["depth"], old_slots=g["old_slots"], new_slots=g["new_slots"], moved=g["moved"],
+                                   overflow=g["overflow"], kernel=int(g["kernel"] == "scatter"), rehash_ms=g["rehash_ms"])
+            line = C.create_string_buffer(512)
+            if nat.lib().kmc_growth_report(C.byref(st), line, 512) >= 0:
+                print(line.value.decode())
     if a.verbose and timing:
         print(f"Wall time outside the search: kmc_open {timing['open_s']:.3f}s (HIP initialisation {timing['hip_init_s']:.3f}s, code "
               f"object {timing['code_object_s']:.3f}s, allocation of {timing['device_bytes'] / 2 ** 30:.1f} GiB {timing['alloc_s']:.3f}s), "
