@@ -120,6 +120,7 @@ SYMBOLS = [
     ("kmc_table_growth_enable", C.c_int, [_H, C.c_uint64]),
     ("kmc_table_growth_stats", C.c_uint64, [_H, C.POINTER(KmcGrowthStat), C.c_uint64]),
     ("kmc_code_object_path", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_char_p, C.c_uint64]),
+    ("kmc_table_code_object_path", C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64]),
     ("kmc_run", C.c_int, [_H, PROGRESS_CB, C.c_void_p]),
     ("kmc_result_get", C.c_int, [_H, C.POINTER(KmcResult)]),
     ("kmc_timing_get", C.c_int, [_H, C.POINTER(KmcTiming)]),

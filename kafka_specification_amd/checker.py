@@ -149,6 +149,13 @@ def code_object_path(cfg: CheckerConfig, arch: str = "gfx950") -> str:
     return buf.value.decode()
 
 
+def table_code_object_path(arch: str = "gfx950") -> str:
+    """... and the cached code object of the table kernels (precompile_table), compiled first if it is not there."""
+    buf = C.create_string_buffer(4096)
+    nat.check(nat.lib().kmc_table_code_object_path(arch.encode(), buf, 4096))
+    return buf.value.decode()
+
+
 def elf_sections(blob: bytes) -> dict:
     """{name: bytes} of the sections of a little-endian ELF64 image that occupy file space (an AMDGPU code object)."""
     import struct

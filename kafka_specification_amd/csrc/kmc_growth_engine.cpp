@@ -225,6 +225,17 @@ int kmc_precompile_table(const char* arch) {
     return get_table_code_object(nullptr, arch ? arch : "gfx950", &code);
 }
 
+int kmc_table_code_object_path(const char* arch, char* out, uint64_t cap) {
+    if (!out || !cap) return fail(KMC_E_ARG, "null buffer");
+    std::vector<char> code;
+    std::string path;
+    int rc = get_table_code_object(nullptr, arch ? arch : "gfx950", &code, &path);
+    if (rc) return rc;
+    if (path.size() + 1 > cap) return fail(KMC_E_ARG, "path of %zu bytes does not fit %llu", path.size(), (unsigned long long)cap);
+    memcpy(out, path.c_str(), path.size() + 1);
+    return KMC_OK;
+}
+
 int kmc_table_growth_enable(kmc_handle* h, uint64_t max_slots) {
     if (!h) return fail(KMC_E_ARG, "null handle");
     if (!h->table) return fail(KMC_E_ARG, "host-only handle (device = -1): there is no seen-set to grow");
