@@ -73,7 +73,7 @@ def precompile_list():
     # Kip320 at 6/1/1/0 (4/2/1/1, 7/1/1/0 and the BASELINE bindings are above / below)
     out += [dict(model=m, n_replicas=N, log_size=1, max_records=1, max_leader_epoch=0) for m in KAFKA for N in (4, 5)]
     out += [dict(model="Kip320", n_replicas=6, log_size=1, max_records=1, max_leader_epoch=0)]
-    for M in (0, 1, 10, 1000):
+    for M in (0, 1, 10, 19, 1000):   # (19: one state per level, ending inside kmc_run's second chain of launches)
         out.append(dict(model="IdSequence", max_id=M))
     for K in (1, 2, 3, 4):
         out.append(dict(model="FiniteReplicatedLog", n_replicas=2, log_size=4, n_log_records=K))

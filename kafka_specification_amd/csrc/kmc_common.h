@@ -128,6 +128,8 @@ typedef unsigned int u32;
 
 #define KMC_FLAG_PAIRED 4096u  // a run that keeps traces on 64-bit entries: the slots are 16 bytes, fingerprint + predecessor (KmcArgs::pred
                                // = table + 1, both indexed 2 i) — the claim and its predecessor dirty ONE line instead of two random ones
+#define KMC_FLAG_DEADLOCK_WITNESS 8192u  // kmc_config.check_deadlock: the host reads KmcLevelCtl::deadlock_fp_inv, so a deadlocked state
+                                         // sends its fingerprint there; without it such a state is only counted
 
 // A counter alone on its 128-byte line.  Device-scope atomics serialise per cache line at the
 // memory side (~90 M/s): eight "separate" 8-byte append counters packed into one 64-byte line were

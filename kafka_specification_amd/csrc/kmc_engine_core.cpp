@@ -217,7 +217,8 @@ KmcArgs base_args(kmc_handle* h, int ctl_slot) {
     a.ctl = h->ctl + ctl_slot;
     a.seed = h->cfg.hash_seed;
     a.inv_mask = h->cfg.invariant_mask;
-    a.flags = (h->cfg.keep_trace ? KMC_FLAG_TRACE : 0u) | (h->slot_words == 2 ? KMC_FLAG_FP128 : 0u) | (h->paired ? KMC_FLAG_PAIRED : 0u);
+    a.flags = (h->cfg.keep_trace ? KMC_FLAG_TRACE : 0u) | (h->slot_words == 2 ? KMC_FLAG_FP128 : 0u) | (h->paired ? KMC_FLAG_PAIRED : 0u) |
+              (h->cfg.check_deadlock ? KMC_FLAG_DEADLOCK_WITNESS : 0u);   // (absorb, the only reader of deadlock_fp_inv, reads it under the same condition)
     a.nshards = (uint32_t)h->cfg.n_shards;
     a.shard = (uint32_t)h->cfg.shard_id;
     a.rec_words = (uint32_t)h->rec_words;
