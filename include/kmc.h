@@ -235,6 +235,14 @@ int kmc_timing_get(kmc_handle* h, kmc_timing* out);
  * opened with the same constants, hash seed and capacities, then kmc_resume continues the
  * search as if it had never stopped (max_levels of the new handle applies). */
 int kmc_checkpoint_save(kmc_handle* h, const char* path);
+/* kmc_checkpoint_save_compact (same preconditions) writes the seen-set as its entries with an index instead of as an image of
+ * every slot: the file's size follows what the search has stored, and kmc_checkpoint_load (which tells the two formats apart)
+ * takes it into a handle of ANY table_capacity, a multiple of 64 at which the entries stay below the load limit 0.92 — smaller or
+ * larger than the saved one (KMC_E_ARG names the smallest that would do) — and of any frontier_capacity whose segments hold the
+ * saved ones.  Model, constants, hash seed, shard, fingerprint width, layout, symmetry and the way predecessors are kept must
+ * match as for the classic file.  Afterwards kmc_result.table_capacity / frontier_capacity are the loading handle's.  A file
+ * whose counts do not add up is refused (KMC_E_ARG; KMC_E_STATE where it ends early), a table rebuilt with other than the stored entries ends with KMC_E_DEVICE. */
+int kmc_checkpoint_save_compact(kmc_handle* h, const char* path);
 int kmc_checkpoint_load(kmc_handle* h, const char* path);
 int kmc_resume(kmc_handle* h, kmc_progress_cb cb, void* user);
 /* Let kmc_run / kmc_resume enlarge the seen-set at level boundaries instead of ending with KMC_V_TABLE_FULL (TLC's FPSet grows
@@ -249,8 +257,10 @@ int kmc_resume(kmc_handle* h, kmc_progress_cb cb, void* user);
  * capped by max_slots and by what can be allocated while the old table still exists (when nothing can be had the search
  * goes on in the table it has and ends as it would without growth).  A level is never interrupted and never re-run.
  * Afterwards kmc_result.table_capacity, kmc_contains, kmc_pred_of, kmc_trace and kmc_checkpoint_save follow the new table; a
- * checkpoint is loaded into a handle opened with the table_capacity it was saved at.  A rehash that does not carry over exactly
- * the stored states ends the run with KMC_E_DEVICE.  KMC_REHASH=window|scatter (read here) chooses the kernel: README. */
+ * classic checkpoint is loaded into a handle opened with the table_capacity it was saved at, a compact one
+ * (kmc_checkpoint_save_compact) into a handle of any sufficient capacity, a growing one included.  A rehash that does not carry over exactly
+ * the stored states ends the run with KMC_E_DEVICE.  KMC_REHASH=window|scatter (read here) chooses the kernel, and with KMC_REHASH_WINDOW_KIB
+ * also how this handle loads a compact checkpoint: README. */
 int kmc_table_growth_enable(kmc_handle* h, uint64_t max_slots);
 typedef struct kmc_growth_stat {
     uint64_t depth;        /* the level boundary (depth of the last completed level) */

@@ -125,6 +125,7 @@ SYMBOLS = [
     ("kmc_result_get", C.c_int, [_H, C.POINTER(KmcResult)]),
     ("kmc_timing_get", C.c_int, [_H, C.POINTER(KmcTiming)]),
     ("kmc_checkpoint_save", C.c_int, [_H, C.c_char_p]),
+    ("kmc_checkpoint_save_compact", C.c_int, [_H, C.c_char_p]),
     ("kmc_checkpoint_load", C.c_int, [_H, C.c_char_p]),
     ("kmc_resume", C.c_int, [_H, PROGRESS_CB, C.c_void_p]),
     ("kmc_level_sizes", C.c_uint64, [_H, C.POINTER(C.c_uint64), C.c_uint64]),

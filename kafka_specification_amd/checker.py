@@ -304,8 +304,11 @@ class ModelChecker:
                 for i in range(min(n.value, cap))]
 
     # -- checkpoint / recover (TLC -checkpoint / -recover) ----------------------------------------
-    def save_checkpoint(self, path: str) -> None:
-        nat.check(self._lib.kmc_checkpoint_save(self._h, path.encode()))
+    def save_checkpoint(self, path: str, compact: bool = False) -> None:
+        """compact: the seen-set goes out as its entries, not as an image of every slot, and load_checkpoint takes the file
+        into a checker of any sufficient table_capacity (kmc_checkpoint_save_compact)."""
+        save = self._lib.kmc_checkpoint_save_compact if compact else self._lib.kmc_checkpoint_save
+        nat.check(save(self._h, path.encode()))
 
     def load_checkpoint(self, path: str) -> None:
         nat.check(self._lib.kmc_checkpoint_load(self._h, path.encode()))

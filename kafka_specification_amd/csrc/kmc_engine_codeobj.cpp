@@ -382,7 +382,7 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
 // shape), cached under <cache>/table/ with the compiler's identity in the file name and the pinned compiler's object preferred,
 // as above.  It is compiled from a text of its own (KMC_SRC_REHASH): no model-specialised object changes with it.
 int get_table_code_object(const char* cache_dir, const std::string& arch, std::vector<char>* code, std::string* path_out) {
-    const std::string src = strip_for_concat(KMC_SRC_REHASH) + "\nKMC_REHASH_INSTANTIATE_ALL\n";
+    const std::string src = strip_for_concat(KMC_SRC_REHASH) + "\nKMC_REHASH_INSTANTIATE_ALL\nKMC_COMPACT_INSTANTIATE_ALL\n";
     const std::string top = cache_dir ? std::string(cache_dir) : default_cache_dir();
     const std::string dir = top + "/table";
     std::string path;

@@ -331,7 +331,7 @@ int find_outside_witness(kmc_handle* h, const u64* frontier, const uint64_t seg[
     return KMC_OK;
 }
 
-int reset_run(kmc_handle* h) {
+int reset_run(kmc_handle* h, bool clear_seen_set) {
     // (Clearing a second table on a side stream in the shadow of the run — a double-buffered seen-set — was measured in
     // round 3: the step got 0.4 ms shorter, but the memset's own kernel competes with the first, small levels and their
     // launches got 0.9 ms longer in total; dropped, profiles/r03_step_overhead.txt.)
@@ -340,6 +340,7 @@ int reset_run(kmc_handle* h) {
         HIP_TRY(hipEventCreate(&h->ev_aux[0]));
         HIP_TRY(hipEventCreate(&h->ev_aux[1]));
     }
+    if (clear_seen_set) {
     range_push("kmc clear seen-set %s", h->kname.c_str());
     HIP_TRY(hipEventRecord(h->ev_aux[0], h->stream));
     HIP_TRY(hipMemsetAsync(h->table, 0, h->table_cap * h->stride_words() * 8, h->stream));
@@ -347,7 +348,8 @@ int reset_run(kmc_handle* h) {
     HIP_TRY(hipEventRecord(h->ev_aux[1], h->stream));
     range_pop();
     h->clear_pending = true;   // (its duration is read where the stream is next waited for: do_begin)
-    if (!h->first_clear_timed) {   // the first clear of a handle touches freshly mapped memory: timed once, by waiting for it
+    }
+    if (clear_seen_set && !h->first_clear_timed) {   // the first clear of a handle touches freshly mapped memory: timed once, by waiting for it
         h->first_clear_timed = true;
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->timing.first_clear_s = now_s() - t_clear0;

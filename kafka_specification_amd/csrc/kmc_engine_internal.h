@@ -9,6 +9,7 @@
 //   kmc_engine_step.cpp      checkpoint / recover, the level-step interface of one shard
 //   kmc_sim_engine.cpp       random simulation: kmc_simulate / kmc_simulate_walk / kmc_sim_draw over k_simulate (the fourth code object)
 //   kmc_growth_engine.cpp    the growing seen-set: kmc_table_growth_enable / _stats, when and how far (grow_if_needed), the rehash launches
+//   kmc_ckpt_compact.cpp     the compact checkpoint's table part: the launches of kmc_compact.h's pack / unpack kernels, the stretches in the file
 //   kmc_engine_exchange.cpp  the per-level exchange: RCCL bound with dlopen, the plan, one-shot and pipelined levels, logical shards
 // The engine stands in for TLC's ModelChecker + Worker threads [TLC-recall; TLC is not part of /root/reference].  No CPU fallback
 // exists: without a HIP device or compiler every entry point fails with KMC_E_DEVICE / KMC_E_COMPILE.
@@ -36,6 +37,7 @@
 #pragma clang diagnostic ignored "-Wunused-parameter"
 #include "kmc_device.h"   // host-visible parts: KmcArgs, KmcLevelCtl, layout, fingerprint
 #include "kmc_rehash.h"   // ... and of the growing seen-set's code object: KmcRehashArgs, KmcRehashCtl
+#include "kmc_compact.h"  // ... and KmcCompactArgs of its pack / unpack kernels
 #pragma clang diagnostic pop
 
 // Levels kmc_run queues back to back before it waits (no progress callback): see run_levels.
@@ -97,6 +99,7 @@ struct kmc_growth {
     uint64_t window_bytes = 32 * 1024;      // KMC_REHASH_WINDOW_KIB: LDS of one window (32 KiB: profiles/table_growth.json)
     hipModule_t mod = nullptr;              // the table code object (kmc_rehash.h), joined on first use
     hipFunction_t f_window = nullptr, f_overflow = nullptr, f_scatter = nullptr;
+    hipFunction_t f_pack_count = nullptr, f_pack_scan = nullptr, f_pack_write = nullptr, f_unpack = nullptr;   // kmc_compact.h (kmc_ckpt_compact.cpp)
     KmcRehashCtl* ctl = nullptr;            // device
     KmcRehashCtl* ctl_host = nullptr;       // pinned
     std::vector<kmc_growth_stat> stats;     // of the last run
@@ -251,7 +254,7 @@ int zero_ctl(kmc_handle* h, int slot);
 uint64_t produced_segments(kmc_handle* h, const KmcLevelCtl& c, uint64_t seg[KMC_SEGS]);
 int find_state(kmc_handle* h, const u64* frontier, const uint64_t seg[KMC_SEGS], uint64_t fp, std::vector<uint64_t>* out);
 int find_outside_witness(kmc_handle* h, const u64* frontier, const uint64_t seg[KMC_SEGS], uint64_t fp);
-int reset_run(kmc_handle* h);
+int reset_run(kmc_handle* h, bool clear_seen_set = true);   // (false: a compact checkpoint is about to write every slot)
 uint64_t weighted(const kmc_handle* h, uint64_t raw, uint64_t corr);
 uint64_t queue_now(const kmc_handle* h);
 void book_level(kmc_handle* h, uint64_t produced, const KmcLevelCtl& c);
@@ -283,6 +286,29 @@ uint64_t auto_frontier_capacity(const kmc_handle* h, double budget);
 // at a level boundary of run_levels, on a handle with growth enabled: enlarges the seen-set when the load rule or the safety rule asks
 int grow_if_needed(kmc_handle* h);
 void growth_release(kmc_handle* h);   // at kmc_close
+// the table code object joins the handle (from the cache; a cold cache compiles it: kmc_precompile_table), with its control block
+int table_kernels_ensure(kmc_handle* h);
+// words of an entry: the slot's, and the predecessor's where those have a table of their own
+inline bool separate_pred(const kmc_handle* h) { return h->pred && !h->paired; }
+inline uint64_t entry_words(const kmc_handle* h) { return h->stride_words() + (separate_pred(h) ? 1 : 0); }
+
+// ---- kmc_engine_step.cpp / kmc_ckpt_compact.cpp: the compact checkpoint (magic KMCCKPC1) ----
+struct CkptCompact {         // follows the header both formats share
+    uint64_t n_entries;      // entries of the seen-set = kmc_result.orbit_representatives
+    uint64_t entry_words;    // 1..3: the slot's words and, with a predecessor table of its own, that word
+    uint64_t tile;           // KMC_COMPACT_TILE of the build that wrote the file
+    uint64_t stretch_groups; // 64-slot groups per stretch (a multiple of tile): stretch k is the groups [k s, min((k + 1) s, G))
+};
+// where the wall time of one save or load went (KMC_VERBOSE prints it; tools/ckpt_bench.py reads that line)
+struct CkptClock {
+    double kernel_ms = 0, copy_s = 0, io_s = 0;   // HIP events around the kernels; device <-> host copies with their waits; fread / fwrite
+};
+int checkpoint_save(kmc_handle* h, const char* path, bool compact);   // both formats' preconditions, header, frontier
+CkptCompact compact_describe(const kmc_handle* h);
+int compact_save_table(kmc_handle* h, FILE* f, const CkptCompact& ch, CkptClock* clk);
+// the file is not trusted: what its header says against this handle, before anything is sized by it
+int compact_check_header(const kmc_handle* h, const CkptCompact& ch, uint64_t saved_cap);
+int compact_load_table(kmc_handle* h, FILE* f, const CkptCompact& ch, uint64_t saved_cap, CkptClock* clk);
 
 // ---- kmc_engine_tuning.cpp: what the product's code calls of the tuning aids; no-ops in libkmc.so ----
 #if KMC_TUNING

@@ -5,6 +5,8 @@ using namespace kmc_engine;
 // ---- checkpoint / recover (TLC -checkpoint / -recover [TLC-recall]) --------------------------
 // File: header, kmc_result, level sizes, segment sizes, then the fingerprint table (and the
 // predecessor table when traces are kept) and the current frontier's planes, segment by segment.
+// The compact form (magic KMCCKPC1, kmc_checkpoint_save_compact) has a CkptCompact behind the header and, in the table's
+// place, the seen-set's entries with their index (kmc_ckpt_compact.cpp): it loads into a table of any sufficient size.
 namespace {
 struct CkptHeader {
     char magic[8];          // "KMCCKPT7" (4: before round 5 changed the representative at four replicas; before canon_form.  5: before
@@ -26,14 +28,19 @@ struct CkptHeader {
 uint64_t pred_form(const kmc_handle* h) { return !h->pred ? 0u : h->paired ? 2u : 1u; }
 bool wr(FILE* f, const void* p, size_t n) { return fwrite(p, 1, n, f) == n; }
 bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
+thread_local CkptClock g_clk;   // of the save or load in progress on this thread
 // device <-> file through a bounded pinned staging buffer
 int dev_to_file(FILE* f, const u64* dev, uint64_t words) {
     const uint64_t chunk = 1ull << 24;  // 128 MiB
     std::vector<uint64_t> buf(words < chunk ? words : chunk);
     for (uint64_t at = 0; at < words; at += chunk) {
         const uint64_t n = words - at < chunk ? words - at : chunk;
+        const double t0 = now_s();
         HIP_TRY(hipMemcpy(buf.data(), dev + at, n * 8, hipMemcpyDeviceToHost));
+        const double t1 = now_s();
         if (!wr(f, buf.data(), n * 8)) return fail(KMC_E_STATE, "checkpoint: short write");
+        g_clk.copy_s += t1 - t0;
+        g_clk.io_s += now_s() - t1;
     }
     return KMC_OK;
 }
@@ -42,16 +49,23 @@ int file_to_dev(FILE* f, u64* dev, uint64_t words) {
     std::vector<uint64_t> buf(words < chunk ? words : chunk);
     for (uint64_t at = 0; at < words; at += chunk) {
         const uint64_t n = words - at < chunk ? words - at : chunk;
+        const double t0 = now_s();
         if (!rd(f, buf.data(), n * 8)) return fail(KMC_E_STATE, "checkpoint: short read");
+        const double t1 = now_s();
         HIP_TRY(hipMemcpy(dev + at, buf.data(), n * 8, hipMemcpyHostToDevice));
+        g_clk.io_s += t1 - t0;
+        g_clk.copy_s += now_s() - t1;
     }
     return KMC_OK;
 }
+void report(const kmc_handle* h, const char* what, bool compact, double t0) {
+    if (h->knobs.verbose)
+        fprintf(stderr, "[kmc] checkpoint %s (%s): %.3f ms in all; kernels %.3f ms, device <-> host copies %.3f ms, file I/O %.3f ms\n", what,
+                compact ? "compact" : "classic", 1e3 * (now_s() - t0), g_clk.kernel_ms, 1e3 * g_clk.copy_s, 1e3 * g_clk.io_s);
+}
 }  // namespace
 
-extern "C" {
-
-int kmc_checkpoint_save(kmc_handle* h, const char* path) {
+int kmc_engine::checkpoint_save(kmc_handle* h, const char* path, bool compact) {
     if (!h || !path) return fail(KMC_E_ARG, "null argument");
     if (!h->table) return fail(KMC_E_STATE, "checkpoints are for device handles");
     // a shard of a multi-GPU search (level-step interface) saves its own table / frontier between kmc_step_finish and
@@ -72,6 +86,7 @@ int kmc_checkpoint_save(kmc_handle* h, const char* path) {
     if (!f) return fail(KMC_E_ARG, "cannot open %s for writing", path);
     CkptHeader hd{};
     memcpy(hd.magic, "KMCCKPT7", 8);
+    if (compact) memcpy(hd.magic, "KMCCKPC1", 8);
     hd.cfg = h->cfg;
     hd.cfg.cache_dir = nullptr;
     hd.table_cap = h->table_cap; hd.fcap = h->fcap; hd.seg_cap = h->seg_cap; hd.level = h->level;
@@ -79,18 +94,30 @@ int kmc_checkpoint_save(kmc_handle* h, const char* path) {
     hd.layout_form = (uint64_t)h->lay.rm;
     hd.canon_form = (uint64_t)KMC_SYMM_UNROLLED_MAX;
     int rc = KMC_OK;
-    bool ok = wr(f, &hd, sizeof hd) && wr(f, &h->res, sizeof h->res) && wr(f, h->levels.data(), h->levels.size() * 8) &&
+    g_clk = CkptClock();
+    const double t0 = now_s();
+    const CkptCompact ch = compact_describe(h);
+    bool ok = wr(f, &hd, sizeof hd) && (!compact || wr(f, &ch, sizeof ch)) && wr(f, &h->res, sizeof h->res) && wr(f, h->levels.data(), h->levels.size() * 8) &&
               wr(f, h->seg_n, sizeof h->seg_n) && wr(f, h->init_words.data(), h->W * 8);
     if (!ok) rc = fail(KMC_E_STATE, "checkpoint: short write");
-    if (!rc) rc = dev_to_file(f, h->table, h->table_cap * h->stride_words());
-    if (!rc && h->pred && !h->paired) rc = dev_to_file(f, h->pred, h->table_cap);
+    if (compact) {
+        if (!rc) rc = compact_save_table(h, f, ch, &g_clk);
+    } else {
+        if (!rc) rc = dev_to_file(f, h->table, h->table_cap * h->stride_words());
+        if (!rc && h->pred && !h->paired) rc = dev_to_file(f, h->pred, h->table_cap);
+    }
     for (int sg = 0; sg < KMC_SEGS && !rc; ++sg)
         for (int k = 0; k < h->planes && !rc; ++k)
             if (h->seg_n[sg])
                 rc = dev_to_file(f, h->frontier[h->cur] + (uint64_t)k * h->fcap + (uint64_t)sg * h->seg_cap, h->seg_n[sg]);
     fclose(f);
+    if (!rc) report(h, "save", compact, t0);
     return rc;
 }
+
+extern "C" {
+
+int kmc_checkpoint_save(kmc_handle* h, const char* path) { return checkpoint_save(h, path, false); }
 
 int kmc_checkpoint_load(kmc_handle* h, const char* path) {
     if (!h || !path) return fail(KMC_E_ARG, "null argument");
@@ -100,7 +127,12 @@ int kmc_checkpoint_load(kmc_handle* h, const char* path) {
     if (!f) return fail(KMC_E_ARG, "cannot open %s", path);
     CkptHeader hd{};
     int rc = KMC_OK;
-    if (!rd(f, &hd, sizeof hd) || memcmp(hd.magic, "KMCCKPT7", 8) != 0)
+    g_clk = CkptClock();
+    const double t0 = now_s();
+    const bool got = rd(f, &hd, sizeof hd);
+    const bool compact = got && memcmp(hd.magic, "KMCCKPC1", 8) == 0;
+    CkptCompact ch{};
+    if (!got || (!compact && memcmp(hd.magic, "KMCCKPT7", 8) != 0) || (compact && !rd(f, &ch, sizeof ch)))
         rc = fail(KMC_E_ARG, "%s is not a checkpoint of this version", path);
     const kmc_config& a = hd.cfg;
     const kmc_config& b = h->cfg;
@@ -109,10 +141,16 @@ int kmc_checkpoint_load(kmc_handle* h, const char* path) {
                 a.n_log_records != b.n_log_records || a.max_id != b.max_id || a.hash_seed != b.hash_seed ||
                 a.n_shards != b.n_shards || a.shard_id != b.shard_id || hd.w != (uint64_t)h->W ||
                 hd.layout_form != (uint64_t)h->lay.rm || (a.wide_fingerprint != 0) != (b.wide_fingerprint != 0) ||
-                (a.symmetry != 0) != (b.symmetry != 0) || (b.symmetry && hd.canon_form != (uint64_t)KMC_SYMM_UNROLLED_MAX)))
+                (a.symmetry != 0) != (b.symmetry != 0) || (b.symmetry && hd.canon_form != (uint64_t)KMC_SYMM_UNROLLED_MAX) ||
+                (compact && hd.has_pred != pred_form(h))))
         rc = fail(KMC_E_ARG, "checkpoint was taken for a different model / constants / hash seed / shard / fingerprint width / "
-                             "state layout / symmetry setting / orbit representative");
-    if (!rc && (hd.table_cap != h->table_cap || hd.fcap != h->fcap || hd.seg_cap != h->seg_cap ||
+                             "state layout / symmetry setting / orbit representative%s", compact ? " / way of keeping predecessors" : "");
+    // (a compact file is held to no capacity but a sufficient one: the table is rebuilt from its entries, and the planes of a
+    // frontier are addressed by the handle's own fcap / seg_cap — a state's segment is the workgroup that appended it, never a
+    // function of seg_cap, so a saved segment only has to fit the handle's)
+    if (!rc && compact) rc = compact_check_header(h, ch, hd.table_cap);
+    if (!rc && compact) hd.fcap = h->fcap;
+    if (!rc && !compact && (hd.table_cap != h->table_cap || hd.fcap != h->fcap || hd.seg_cap != h->seg_cap ||
                 hd.has_pred != pred_form(h)))
         rc = fail(KMC_E_ARG, "checkpoint capacities differ: open the handle with table_capacity=%llu frontier_capacity=%llu keep_trace=%d",
                   (unsigned long long)hd.table_cap, (unsigned long long)hd.fcap, (int)(hd.has_pred != 0));
@@ -126,7 +164,9 @@ int kmc_checkpoint_load(kmc_handle* h, const char* path) {
     // are still booked for a conservation check that belongs to the abandoned level)
     if (!rc && h->xstream && hipStreamSynchronize(h->xstream) != hipSuccess) rc = fail(KMC_E_DEVICE, "stream sync failed");
     if (!rc) h->inserted_level = 0;
-    if (!rc) rc = reset_run(h);
+    // (a compact file's table is written slot by slot by the unpack: no clear ahead of it — but after a load that fails, below)
+    const bool uncleared = !rc && compact;
+    if (!rc) rc = reset_run(h, !compact);
     if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(KMC_E_DEVICE, "stream sync failed");
     if (!rc) {
         kmc_result saved{};
@@ -147,28 +187,41 @@ int kmc_checkpoint_load(kmc_handle* h, const char* path) {
         if (!rc && (seg_sum != hd.n_cur || (!h->cfg.symmetry && lv.back() != hd.n_cur) || lv_sum != saved.distinct ||
                     saved.orbit_representatives > h->table_cap || saved.orbit_representatives > saved.distinct ||
                     saved.verdict != KMC_V_LEVEL_LIMIT || saved.state_words != (uint64_t)h->W ||
-                    saved.table_capacity != h->table_cap || saved.frontier_capacity != h->fcap))
+                    (compact ? saved.table_capacity != hd.table_cap || saved.orbit_representatives != ch.n_entries
+                             : saved.table_capacity != h->table_cap || saved.frontier_capacity != h->fcap)))
             rc = fail(KMC_E_ARG, "checkpoint body is inconsistent with its header / this handle");
         if (!rc && kmc_fingerprint_of(h, init.data()) == 0) rc = fail(KMC_E_ARG, "checkpoint: bad initial state");
         if (!rc) {
             h->res = saved;
+            h->res.table_capacity = h->table_cap;      // (a compact file's may differ: the result speaks of this handle)
+            h->res.frontier_capacity = h->fcap;
             h->levels = lv;
             memcpy(h->seg_n, segs, sizeof segs);
             h->init_words = init;
         }
     }
-    if (!rc) rc = file_to_dev(f, h->table, h->table_cap * h->stride_words());
-    if (!rc && h->pred && !h->paired) rc = file_to_dev(f, h->pred, h->table_cap);
+    if (compact) {
+        if (!rc) rc = compact_load_table(h, f, ch, hd.table_cap, &g_clk);
+    } else {
+        if (!rc) rc = file_to_dev(f, h->table, h->table_cap * h->stride_words());
+        if (!rc && h->pred && !h->paired) rc = file_to_dev(f, h->pred, h->table_cap);
+    }
     h->cur = 0;
     for (int sg = 0; sg < KMC_SEGS && !rc; ++sg)
         for (int k = 0; k < h->planes && !rc; ++k)
             if (h->seg_n[sg])
                 rc = file_to_dev(f, h->frontier[0] + (uint64_t)k * h->fcap + (uint64_t)sg * h->seg_cap, h->seg_n[sg]);
     fclose(f);
+    if (rc && uncleared) {   // the handle is left as a failed classic load leaves it: an empty seen-set
+        (void)hipMemsetAsync(h->table, 0, h->table_cap * h->stride_words() * 8, h->stream);
+        if (h->pred && !h->paired) (void)hipMemsetAsync(h->pred, 0, h->table_cap * 8, h->stream);
+        (void)hipStreamSynchronize(h->stream);
+    }
     if (rc) return rc;
     h->level = hd.level;
     h->n_cur = hd.n_cur;
     h->restored = true;
+    report(h, "load", compact, t0);
     return KMC_OK;
 }
 

@@ -14,16 +14,10 @@ void growth_release(kmc_handle* h) {
     g.ctl = g.ctl_host = nullptr;
     g.mod = nullptr;
     g.f_window = g.f_overflow = g.f_scatter = nullptr;
+    g.f_pack_count = g.f_pack_scan = g.f_pack_write = g.f_unpack = nullptr;
 }
 
-}  // namespace kmc_engine
-
-// words of an entry: the slot's, and the predecessor's where those have a table of their own
-static bool separate_pred(const kmc_handle* h) { return h->pred && !h->paired; }
-static uint64_t entry_words(const kmc_handle* h) { return h->stride_words() + (separate_pred(h) ? 1 : 0); }
-
-// the table code object joins the handle (from the cache; a cold cache compiles it: kmc_precompile_table), with its control block
-static int growth_ensure(kmc_handle* h) {
+int table_kernels_ensure(kmc_handle* h) {
     kmc_growth& g = h->growth;
     if (!g.f_window) {
         std::vector<char> code;
@@ -34,9 +28,14 @@ static int growth_ensure(kmc_handle* h) {
         HIP_TRY(hipModuleGetFunction(&g.f_window, g.mod, ("kmc_rehash_window_" + tag).c_str()));
         HIP_TRY(hipModuleGetFunction(&g.f_overflow, g.mod, ("kmc_rehash_overflow_" + tag).c_str()));
         HIP_TRY(hipModuleGetFunction(&g.f_scatter, g.mod, ("kmc_rehash_scatter_" + tag).c_str()));
+        HIP_TRY(hipModuleGetFunction(&g.f_pack_count, g.mod, ("kmc_pack_count_" + tag).c_str()));
+        HIP_TRY(hipModuleGetFunction(&g.f_pack_scan, g.mod, "kmc_pack_scan"));
+        HIP_TRY(hipModuleGetFunction(&g.f_pack_write, g.mod, ("kmc_pack_write_" + tag).c_str()));
+        HIP_TRY(hipModuleGetFunction(&g.f_unpack, g.mod, ("kmc_unpack_window_" + tag).c_str()));
         // (more than 64 KiB of dynamic LDS has to be asked for; a window the device refuses is an error, never another size)
         if (g.window_bytes > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute((const void*)g.f_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.window_bytes);
+            hipError_t e = hipFuncSetAttribute((const void*)g.f_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.window_bytes);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)g.f_unpack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.window_bytes);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 (void)hipModuleUnload(g.mod);
@@ -51,6 +50,8 @@ static int growth_ensure(kmc_handle* h) {
     if (!g.ctl_host) HIP_TRY(hipHostMalloc(&g.ctl_host, sizeof(KmcRehashCtl)));
     return KMC_OK;
 }
+
+}  // namespace kmc_engine
 
 static int rehash_launch(kmc_handle* h, hipFunction_t f, KmcRehashArgs a, uint64_t blocks, unsigned lds) {
     if (blocks < 1) blocks = 1;
@@ -158,7 +159,7 @@ int grow_if_needed(kmc_handle* h) {
     uint64_t want = 4 * stored > safe ? 4 * stored : safe;
     if (want < 2 * h->table_cap) want = 2 * h->table_cap;
     uint64_t tries[2] = {fit(want), fit(safe)};
-    int rc = growth_ensure(h);
+    int rc = table_kernels_ensure(h);
     if (rc) return rc;
     for (int k = 0; k < 2; ++k) {
         const uint64_t new_cap = tries[k];
@@ -254,6 +255,7 @@ int kmc_table_growth_enable(kmc_handle* h, uint64_t max_slots) {
     const long long kib = env_int("KMC_REHASH_WINDOW_KIB", 32);
     if (kib < 4 || kib > 159) return fail(KMC_E_ARG, "KMC_REHASH_WINDOW_KIB=%lld: a window takes between 4 and 159 KiB of LDS", kib);
     g.window_bytes = (uint64_t)kib * 1024;
+    if (g.mod) growth_release(h);   // (joined by a checkpoint before this call: it joins again, its LDS limit raised for this window)
     g.max_slots = max_slots / 64 * 64;
     // Frontiers that kmc_open sized by itself were clipped to the table (a level cannot outgrow the seen-set): a growing handle's
     // are sized as beside an automatic table (auto_frontier_capacity, kmc_engine_open.cpp) or the level that no

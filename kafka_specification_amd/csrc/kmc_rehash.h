@@ -79,6 +79,62 @@ KMC_DEV bool kmc_rehash_load(const KmcRehashArgs& a, u64 i, u64* e) {
     return e[0] != 0ull;
 }
 
+// One entry goes into the LDS window of the new slots [lo, hi): a linear probe from its home, never past the window's end.
+// false: the window turns it away (home outside, or the chain runs off the end).
+template <int SW, bool SP>
+KMC_DEV bool kmc_window_place(u64* win, u64* wpred, const u64* e, u64 home, u64 lo, u64 hi) {
+    if (home < lo || home >= hi) return false;
+    for (u64 p = home - lo; p < hi - lo; ++p) {
+        if (atomicCAS(&win[p * SW], 0ull, e[0]) == 0ull) {   // ds_cmpst_rtn_b64
+            if constexpr (SW == 2) win[p * SW + 1] = e[1];
+            if constexpr (SP) wpred[p] = e[SW];
+            return true;
+        }
+    }
+    return false;
+}
+
+// The entries a window turned away (`over`, whole waves call this): one atomicAdd per wave, then every lane writes its own record
+template <int EW>
+KMC_DEV void kmc_window_list(const KmcRehashArgs& a, bool over, const u64* e) {
+    const u64 m = __ballot(over);
+    if (!m) return;
+    u64 at = 0;
+    if (kmc_lane() == 0) at = atomicAdd(&a.ctl->listed.v, (u64)__popcll(m));
+    at = kmc_bcast64(at, 0) + kmc_rank_in(m);
+    if (over) {
+        if (at < a.list_cap) {
+#pragma unroll
+            for (int k = 0; k < EW; ++k) a.list[at * EW + k] = e[k];
+        } else {
+            atomicOr(&a.ctl->err, KMC_REHASH_ERR_LIST_FULL);
+        }
+    }
+}
+
+// The whole window goes out, zeros included, 16 bytes per lane and 1 KiB per wave and store: every new slot is written
+// exactly once, by the tile that owns it.  A lane zeroes what it has read: the window is clean for the next tile.
+template <int SW, bool SP>
+KMC_DEV void kmc_window_flush(const KmcRehashArgs& a, u64* win, u64* wpred, u64 lo, u64 nsl) {
+    const u32 tid = threadIdx.x;
+    {
+        KmcSlot2R* const out = (KmcSlot2R*)(a.new_tab + lo * SW);
+        KmcSlot2R* const src = (KmcSlot2R*)win;
+        for (u64 j = tid; j < nsl * SW / 2; j += KMC_REHASH_BLOCK) {
+            out[j] = src[j];
+            src[j] = KmcSlot2R(0ull);
+        }
+    }
+    if constexpr (SP) {
+        KmcSlot2R* const out = (KmcSlot2R*)(a.new_pred + lo);
+        KmcSlot2R* const src = (KmcSlot2R*)wpred;
+        for (u64 j = tid; j < nsl / 2; j += KMC_REHASH_BLOCK) {
+            out[j] = src[j];
+            src[j] = KmcSlot2R(0ull);
+        }
+    }
+}
+
 template <int SW, bool SP>
 KMC_DEV void kmc_rehash_window_body(const KmcRehashArgs& a, u64* lds) {
     constexpr int EW = SW + (SP ? 1 : 0);
@@ -103,55 +159,13 @@ KMC_DEV void kmc_rehash_window_body(const KmcRehashArgs& a, u64* lds) {
             u64 e[EW];
             bool over = false;
             if (i < g1 << 6 && kmc_rehash_load<SW, SP>(a, i, e)) {
-                const u64 home = kmc_slot_of(e[0], a.new_cap);
-                over = true;
-                if (home >= lo && home < hi) {
-                    for (u64 p = home - lo; p < nsl; ++p) {
-                        if (atomicCAS(&win[p * SW], 0ull, e[0]) == 0ull) {   // ds_cmpst_rtn_b64
-                            if constexpr (SW == 2) win[p * SW + 1] = e[1];
-                            if constexpr (SP) wpred[p] = e[SW];
-                            over = false;
-                            ++placed;
-                            break;
-                        }
-                    }
-                }
+                over = !kmc_window_place<SW, SP>(win, wpred, e, kmc_slot_of(e[0], a.new_cap), lo, hi);
+                placed += over ? 0u : 1u;
             }
-            // the entries this window turned away: one atomicAdd per wave, then every lane writes its own record
-            const u64 m = __ballot(over);
-            if (m) {
-                u64 at = 0;
-                if (kmc_lane() == 0) at = atomicAdd(&a.ctl->listed.v, (u64)__popcll(m));
-                at = kmc_bcast64(at, 0) + kmc_rank_in(m);
-                if (over) {
-                    if (at < a.list_cap) {
-#pragma unroll
-                        for (int k = 0; k < EW; ++k) a.list[at * EW + k] = e[k];
-                    } else {
-                        atomicOr(&a.ctl->err, KMC_REHASH_ERR_LIST_FULL);
-                    }
-                }
-            }
+            kmc_window_list<EW>(a, over, e);
         }
         __syncthreads();
-        // the whole window goes out, zeros included, 16 bytes per lane and 1 KiB per wave and store: every new slot is written
-        // exactly once, by the tile that owns it.  A lane zeroes what it has read: the window is clean for the next tile.
-        {
-            KmcSlot2R* const out = (KmcSlot2R*)(a.new_tab + lo * SW);
-            KmcSlot2R* const src = (KmcSlot2R*)win;
-            for (u64 j = tid; j < nsl * SW / 2; j += KMC_REHASH_BLOCK) {
-                out[j] = src[j];
-                src[j] = KmcSlot2R(0ull);
-            }
-        }
-        if constexpr (SP) {
-            KmcSlot2R* const out = (KmcSlot2R*)(a.new_pred + lo);
-            KmcSlot2R* const src = (KmcSlot2R*)wpred;
-            for (u64 j = tid; j < nsl / 2; j += KMC_REHASH_BLOCK) {
-                out[j] = src[j];
-                src[j] = KmcSlot2R(0ull);
-            }
-        }
+        kmc_window_flush<SW, SP>(a, win, wpred, lo, nsl);
     }
     placed = kmc_wave_sum(placed);
     if (placed && kmc_lane() == 0) atomicAdd(&a.ctl->placed_window, (u64)placed);
