@@ -204,10 +204,12 @@ int kmc_open(const kmc_config* cfg, kmc_handle** out);
  * kmc_precompile builds all three; kmc_precompile_mode one of them (mode 0 / 1 / 2 in that order, -1 = all), so that a build
  * script can spread them over its workers.  The fourth object, k_simulate (random simulation, below), is asked for by name:
  * kmc_precompile_simulate, for the configurations that are walked; its cached file is tagged -simulate the way the others are
- * tagged -sharded / -enum. */
+ * tagged -sharded / -enum.  Likewise the batch kernels (kmc_successors_batch, below): kmc_precompile_batch, tagged -batch, cached
+ * under <cache>/batch/. */
 int kmc_precompile(const kmc_config* cfg, const char* arch);
 int kmc_precompile_mode(const kmc_config* cfg, const char* arch, int32_t mode);
 int kmc_precompile_simulate(const kmc_config* cfg, const char* arch);
+int kmc_precompile_batch(const kmc_config* cfg, const char* arch);
 /* The fifth object is model-independent: the kernels that move a seen-set into a larger one (kmc_table_growth_enable, below),
  * one build for every configuration, cached under <cache>/table/.  No GPU needed. */
 int kmc_precompile_table(const char* arch);
@@ -318,13 +320,45 @@ int kmc_frontier_states(kmc_handle* h, uint64_t* words, uint64_t cap_states, uin
 /* All successors of one packed state, straight from the device kernels: writes up to cap
  * records of (state_words + 2) uint64: state, fingerprint, action kind — TLC's enumeration of Next on that state: one
  * record per satisfying binding AND disjunct (a successor that two disjuncts of one binding yield, Kip279.tla:47-51 /
- * Kip320.tla:82-83, is listed twice, as `generated` counts it). */
+ * Kip320.tla:82-83, is listed twice, as `generated` counts it).  The order of the records is not defined here (the kernel appends
+ * them as it finds them); kmc_successors_batch lists the same records in a defined order.  One launch and one wait per call:
+ * a caller with many states wants the batched form. */
 int kmc_successors(kmc_handle* h, const uint64_t* words, uint64_t* out, uint64_t cap, uint64_t* n_out);
 /* The invariants (KMC_INV_* bits of `mask`, whatever cfg->invariant_mask says) each of n packed states violates, from
  * the device's own predicate — the one k_expand applies to the states it expands (TypeOk / WeakIsr / StrongIsr /
  * LeaderInIsr: KafkaReplication.tla:101,320,334,345).  With kmc_successors this is the per-state differential surface:
  * Next and the invariants on any state, reachable or not. */
 int kmc_check_states(kmc_handle* h, const uint64_t* words, uint64_t n, uint32_t mask, uint32_t* violated);
+/* The batched form of the two above (csrc/kmc_batch.h, kmc_batch_engine.cpp): n packed states in ([n][state_words], as
+ * kmc_frontier_states hands them out), a CSR of their successor records out — state i's records are
+ * records[offsets[i] .. offsets[i + 1]), each state_words + 2 uint64 (state, fingerprint, action kind) as kmc_successors writes
+ * them — and the invariants each state violates, from three kernels per launch of states_per_launch states instead of a launch
+ * per state.
+ * THE ORDER OF A STATE'S RECORDS IS CONTRACTUAL: instance order — action kinds in the module's order, the bindings of a kind
+ * ascending, the two records of a binding that satisfies two disjuncts adjacent.  It is the numbering of random simulation:
+ * record r of the batch enumeration of s_t is the candidate that kmc_sim_draw(seed, w, t, n_t) = r takes, and n_t is the state's
+ * count offsets[i + 1] - offsets[i].
+ * All buffers are the caller's host buffers.  `offsets` (n + 1 entries) is always complete and out->records = offsets[n], whether
+ * or not the records fitted: a state's records are written only when its whole run lies below cap_records, so a caller compares
+ * out->records with its cap and calls again.  records may be NULL with cap_records = 0: counts and invariants only — the batched
+ * kmc_check_states.  violated (n entries) may be NULL.  n = 0 is valid: offsets[0] = 0 and no launch.
+ * Refused: host-only handles (KMC_E_STATE); KMC_ASYNC_ISR, for the reason kmc_simulate gives, handles opened with `symmetry`
+ * (kmc_successors stays the way to enumerate under orbit counting) and states_per_launch beyond 2^22 (KMC_E_ARG); staging that
+ * cannot be allocated (KMC_E_NOMEM).  The seen-set, the frontiers and the search's control blocks are not touched: a batch
+ * between two kmc_run changes nothing the second one sees. */
+typedef struct kmc_batch_config {
+    uint32_t inv_mask;           /* KMC_INV_* bits evaluated per state, whatever cfg.invariant_mask says; 0: none */
+    uint32_t states_per_launch;  /* 0 = 2^20; at most 2^22 */
+} kmc_batch_config;
+typedef struct kmc_batch_result {
+    uint64_t states, records;    /* records = offsets[n]: the whole enumeration, whether or not it fitted */
+    uint64_t launches;           /* batches run (three kernels each) */
+    double seconds_total, seconds_kernel;
+    double seconds_count, seconds_scan, seconds_emit;   /* of seconds_kernel: the three kernels, HIP events around each */
+} kmc_batch_result;
+int kmc_successors_batch(kmc_handle* h, const kmc_batch_config* bc, const uint64_t* words, uint64_t n,
+                         uint64_t* offsets /* n + 1 */, uint64_t* records, uint64_t cap_records,
+                         uint32_t* violated /* n, may be NULL */, kmc_batch_result* out);
 /* Counterexample of the last run (needs keep_trace): canonical-byte states from the initial
  * state to the witness, with the action kind that produced each (-1 for the initial state). */
 int kmc_trace(kmc_handle* h, uint8_t* canon_states, int32_t* kinds, uint64_t cap, uint64_t* n_out);
@@ -424,8 +458,8 @@ int kmc_exchange_plan(const uint64_t* counts, int32_t n_shards, int32_t me, uint
  * A walk is a pure function of the model constants, `seed` and the walk's index w — never of the batch, the grid or the
  * device.  State 0 is Init.  At step t the walk stands on state s_t; its candidates are TLC's enumeration of Next on s_t,
  * exactly the records kmc_successors lists (n_t of them; a successor two disjuncts of one binding yield counts twice); it
- * takes record r_t = kmc_sim_draw(seed, w, t, n_t) of them, in an order of its own that is the same for every walk standing
- * on that state.  Every state, Init and the last one included, is checked against cfg.invariant_mask.  The walk ends at the
+ * takes record r_t = kmc_sim_draw(seed, w, t, n_t) of them, in instance order — the order in which kmc_successors_batch
+ * lists the records of s_t, which is contractual (above).  Every state, Init and the last one included, is checked against cfg.invariant_mask.  The walk ends at the
  * first of: a violating state; a state with n_t = 0 (a deadlock under check_deadlock, else just the walk's end); `depth`
  * states (the last of them is checked, its successors are not looked at).
  * Walks run in launches of walks_per_launch, every walker to its own end.  Without continue_on_violation the first launch

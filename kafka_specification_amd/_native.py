@@ -107,6 +107,15 @@ class KmcSimResult(C.Structure):
                 ("seconds_kernel", C.c_double)]
 
 
+class KmcBatchConfig(C.Structure):
+    _fields_ = [("inv_mask", C.c_uint32), ("states_per_launch", C.c_uint32)]
+
+
+class KmcBatchResult(C.Structure):
+    _fields_ = [("states", C.c_uint64), ("records", C.c_uint64), ("launches", C.c_uint64), ("seconds_total", C.c_double),
+                ("seconds_kernel", C.c_double), ("seconds_count", C.c_double), ("seconds_scan", C.c_double), ("seconds_emit", C.c_double)]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.POINTER(KmcLevelInfo), C.c_void_p)
 
 # every symbol include/kmc.h declares: (name, restype, argtypes)
@@ -116,6 +125,7 @@ SYMBOLS = [
     ("kmc_precompile", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
     ("kmc_precompile_mode", C.c_int, [C.POINTER(KmcConfig), C.c_char_p, C.c_int32]),
     ("kmc_precompile_simulate", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
+    ("kmc_precompile_batch", C.c_int, [C.POINTER(KmcConfig), C.c_char_p]),
     ("kmc_precompile_table", C.c_int, [C.c_char_p]),
     ("kmc_table_growth_enable", C.c_int, [_H, C.c_uint64]),
     ("kmc_table_growth_stats", C.c_uint64, [_H, C.POINTER(KmcGrowthStat), C.c_uint64]),
@@ -142,6 +152,9 @@ SYMBOLS = [
     ("kmc_frontier_states", C.c_int, [_H, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
     ("kmc_successors", C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
     ("kmc_check_states", C.c_int, [_H, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+    # batched successors and invariants of states given as data (csrc/kmc_batch_engine.cpp)
+    ("kmc_successors_batch", C.c_int, [_H, C.POINTER(KmcBatchConfig), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(KmcBatchResult)]),
     ("kmc_trace", C.c_int, [_H, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64)]),
     ("kmc_contains", C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     ("kmc_witness", C.c_int, [_H, C.POINTER(C.c_uint64)]),

@@ -131,6 +131,12 @@ def precompile_simulate(cfg: CheckerConfig, arch: str = "gfx950") -> None:
     nat.check(nat.lib().kmc_precompile_simulate(C.byref(c), arch.encode()))
 
 
+def precompile_batch(cfg: CheckerConfig, arch: str = "gfx950") -> None:
+    """... and the batch kernels' code object: ModelChecker.successors_batch of cfg's constants."""
+    c = cfg.to_native()
+    nat.check(nat.lib().kmc_precompile_batch(C.byref(c), arch.encode()))
+
+
 def precompile_table(arch: str = "gfx950") -> None:
     """... and the model-independent fifth: the kernels that move a seen-set into a larger one (ModelChecker.enable_table_growth)."""
     nat.check(nat.lib().kmc_precompile_table(arch.encode()))
@@ -397,6 +403,27 @@ class ModelChecker:
         n = C.c_uint64()
         nat.check(self._lib.kmc_successors(self._h, w, out.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n)))
         return [(tuple(int(x) for x in out[i, :W]), int(out[i, W]), int(out[i, W + 1])) for i in range(min(n.value, cap))]
+
+    def successors_batch(self, states, inv_mask: int = 0, states_per_launch: int = 0):
+        """(offsets, records, violated) of an (n, state_words) uint64 array of packed states: state i's successor records are
+        records[offsets[i]:offsets[i + 1]], rows of state_words + 2 (state, fingerprint, action kind) in instance order — the
+        numbering of random simulation (include/kmc.h, kmc_successors_batch); violated[i] holds the KMC_INV_* bits of inv_mask
+        that state i violates.  A counts-only call sizes the records."""
+        W = self.state_words
+        states = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, W)
+        n = states.shape[0]
+        bc = nat.KmcBatchConfig(inv_mask=inv_mask, states_per_launch=states_per_launch)
+        res = nat.KmcBatchResult()
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        violated = np.zeros(n, dtype=np.uint32)
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+        call = lambda rec, cap: nat.check(self._lib.kmc_successors_batch(
+            self._h, C.byref(bc), p64(states), n, p64(offsets), rec, cap, violated.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(res)))
+        call(None, 0)
+        records = np.zeros((int(res.records), W + 2), dtype=np.uint64)
+        if res.records:
+            call(p64(records), int(res.records))
+        return offsets, records, violated
 
     def contains(self, words) -> bool:
         """Was this packed state reached by the last run?  (FPSet.contains analogue)"""

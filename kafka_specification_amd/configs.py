@@ -207,6 +207,19 @@ def simulate_precompile_list():
             ({kk: v for kk, v in BASELINE_CONFIGS["config4_kip320_7brokers_log8"].items() if kk != "invariants"}, {})]
 
 
+def batch_precompile_list():
+    """(config, environment) pairs whose batch kernels (kmc_precompile_batch: ModelChecker.successors_batch) `build()` specialises:
+    what tests/test_gpu_successors_batch.py enumerates, and the two bindings tools/batch_bench.py measures."""
+    def k(model, N, L, R, E):
+        return dict(model=model, n_replicas=N, log_size=L, max_records=R, max_leader_epoch=E)
+    return [(k("Kip320", 2, 2, 2, 1), {}), (k("Kip279", 3, 2, 2, 2), {}), (k("Kip320", 3, 2, 2, 1), {}),
+            (k("Kip320FirstTry", 3, 2, 2, 2), {}),
+            (dict(model="FiniteReplicatedLog", n_replicas=2, log_size=4, n_log_records=2), {}),
+            (dict(model="IdSequence", max_id=10), {}),
+            ({kk: v for kk, v in HEADLINE.items() if kk != "invariants"}, {}),
+            ({kk: v for kk, v in BASELINE_CONFIGS["config4_kip320_7brokers_log8"].items() if kk != "invariants"}, {})]
+
+
 def layout_variants():
     def c(t):
         return dict(model=t[0], n_replicas=t[1], log_size=t[2], max_records=t[3], max_leader_epoch=t[4])

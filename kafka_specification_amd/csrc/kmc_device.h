@@ -33,7 +33,7 @@
 // not part of /root/reference].
 //
 // The source is split into parts (each cites the spec text it lowers): kmc_common.h, kmc_models_small.h, kmc_kafka.h,
-// kmc_symm.h, kmc_sink.h, kmc_kernels.h, kmc_sim.h (random simulation: k_simulate, a fourth code object).  gen_sources.py embeds them in this order; kmc_engine_codeobj.cpp concatenates them for hiprtc.
+// kmc_symm.h, kmc_sink.h, kmc_kernels.h, kmc_sim.h (random simulation: k_simulate, a fourth code object), kmc_batch.h (batched successors of states given as data: a code object of its own).  gen_sources.py embeds them in this order; kmc_engine_codeobj.cpp concatenates them for hiprtc.
 #pragma once
 #include "kmc_common.h"
 #include "kmc_models_small.h"
@@ -42,3 +42,4 @@
 #include "kmc_sink.h"
 #include "kmc_kernels.h"
 #include "kmc_sim.h"
+#include "kmc_batch.h"

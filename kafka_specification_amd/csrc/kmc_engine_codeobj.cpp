@@ -266,13 +266,14 @@ static int compile_text(const std::string& src, const char* file, const std::vec
 // `mode` = which k_expand the object holds (kmc_kernels.h, KMC_ONLY_MODE): KMC_MODE_LOCAL — the search's own kernel with the
 // small kernels around it — KMC_MODE_SHARDED or KMC_MODE_ENUM; one cached file each, so that a front end which never steps or
 // enumerates never pays for those kernels, and the search's kernel is not recompiled (minutes at seven brokers) for them.
-// (mode 3 = KMC_CODEOBJ_SIM: k_simulate, random simulation — kmc_sim.h)
-extern const char* const MODE_SUFFIX[4] = {"", "_sh", "_en", ""};
-extern const char* const MODE_FILE_TAG[4] = {"", "-sharded", "-enum", "-simulate"};
-extern const char* const MODE_KERNEL[4] = {"kmc_expand", "kmc_expand", "kmc_expand", "kmc_simulate"};
+// (mode 3 = KMC_CODEOBJ_SIM: k_simulate, random simulation — kmc_sim.h; mode 4 = KMC_CODEOBJ_BATCH: k_batch_count / _scan / _emit,
+// batched successors of states given as data — kmc_batch.h)
+extern const char* const MODE_SUFFIX[5] = {"", "_sh", "_en", "", ""};
+extern const char* const MODE_FILE_TAG[5] = {"", "-sharded", "-enum", "-simulate", "-batch"};
+extern const char* const MODE_KERNEL[5] = {"kmc_expand", "kmc_expand", "kmc_expand", "kmc_simulate", "kmc_batch_emit"};
 int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<char>* code, std::string* kname,
                     const char* extra_options, std::string* path_out, unsigned mode, const std::string* jit_defines, int layout_mode) {
-    if (mode > KMC_CODEOBJ_SIM) return fail(KMC_E_ARG, "no code object for mode %u", mode);
+    if (mode > KMC_CODEOBJ_BATCH) return fail(KMC_E_ARG, "no code object for mode %u", mode);
     KmcLayout lay;
     std::string name, inst;
     if (!validate(cfg, &lay, &name, &inst, layout_mode))
@@ -322,7 +323,8 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
     const std::string key = cache_key(src, arch, defines_key);
     // (k_simulate's objects live in a sub-directory of their own: the cache's top level holds the search's objects, one k_expand each)
     const std::string top = cfg.cache_dir ? std::string(cfg.cache_dir) : default_cache_dir();
-    const std::string dir = mode == KMC_CODEOBJ_SIM ? top + "/simulate" : top;
+    // (... and so do the batch kernels')
+    const std::string dir = mode == KMC_CODEOBJ_SIM ? top + "/simulate" : mode == KMC_CODEOBJ_BATCH ? top + "/batch" : top;
     const long long mine = (long long)compiler_id_mine(), pinned = (long long)compiler_id_pinned();
     std::string path;
     const bool cached = cache_fetch(dir, name, arch, key, MODE_FILE_TAG[mode], code, &path);
@@ -351,7 +353,11 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
         for (const std::string& d : defines) opts.push_back(d.c_str());
         const int rc = compile_text(src, "kmc_jit.hip", opts, name.c_str(), code);
         if (rc) return rc;
-        const long spills = expand_vgpr_spills(*code, std::string(MODE_KERNEL[mode]) + MODE_SUFFIX[mode] + "_" + name);
+        long spills = expand_vgpr_spills(*code, std::string(MODE_KERNEL[mode]) + MODE_SUFFIX[mode] + "_" + name);
+        if (mode == KMC_CODEOBJ_BATCH) {   // (two model kernels: the rule holds for the worse of k_batch_emit and k_batch_count)
+            const long sc = expand_vgpr_spills(*code, "kmc_batch_count_" + name);
+            spills = spills < 0 || sc < 0 ? -1 : spills > sc ? spills : sc;
+        }
         if (waves_forced) break;  // an explicit -DKMC_MIN_WAVES (tuning, bug hunts) is taken as given and never cached as default
         // The guard must not pass by accident: an unreadable spill count, or a kernel that still spills at
         // one wave per SIMD, is a failed specialisation — not a kernel to run and cache.
@@ -363,7 +369,8 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
         // (k_simulate is not compiled against KMC_MIN_WAVES — it holds no LDS ring whose size fixes the residency, the compiler has
         // the whole register file of one wave per SIMD — so there is no smaller occupancy target to retry with: the same bound
         // on spilled vector registers holds, and a kernel beyond it is refused)
-        if (waves == 1 || mode == KMC_CODEOBJ_SIM)
+        // (the batch kernels likewise)
+        if (waves == 1 || mode == KMC_CODEOBJ_SIM || mode == KMC_CODEOBJ_BATCH)
             return fail(KMC_E_COMPILE, "%s spills %ld vector registers even at one wave per SIMD: constants too "
                                        "wide for this kernel shape", kernel.c_str(), spills);
         // (these kernels take up to minutes to compile: jump by the size of the overflow, do not crawl)

@@ -8,6 +8,7 @@
 //   kmc_engine_tuning.cpp    ONLY in libkmc_tuning.so (-DKMC_TUNING=1, as the device's tuning build): the dry / shadow passes and launch overrides behind the tuning_* hooks
 //   kmc_engine_step.cpp      checkpoint / recover, the level-step interface of one shard
 //   kmc_sim_engine.cpp       random simulation: kmc_simulate / kmc_simulate_walk / kmc_sim_draw over k_simulate (the fourth code object)
+//   kmc_batch_engine.cpp     batched successors and invariants of states given as data: kmc_successors_batch over k_batch_count / _scan / _emit (a code object of its own)
 //   kmc_growth_engine.cpp    the growing seen-set: kmc_table_growth_enable / _stats, when and how far (grow_if_needed), the rehash launches
 //   kmc_ckpt_compact.cpp     the compact checkpoint's table part: the launches of kmc_compact.h's pack / unpack kernels, the stretches in the file
 //   kmc_engine_exchange.cpp  the per-level exchange: RCCL bound with dlopen, the plan, one-shot and pipelined levels, logical shards
@@ -134,6 +135,19 @@ struct kmc_handle {
     struct { uint64_t seed = 0, first_walk = 0, walks_done = 0, stride = 0; uint32_t depth = 0; bool valid = false; } sim_batch;
     u64* sim_one = nullptr;                  // device: the same for one walker (kmc_simulate_walk's re-run)
     uint64_t sim_one_words = 0;
+    // batched successors of states given as data (kmc_batch_engine.cpp): the kernels' code object and the device staging of a launch
+    struct kmc_batch_state {
+        hipModule_t mod = nullptr;
+        hipFunction_t f_count = nullptr, f_scan = nullptr, f_emit = nullptr;
+        int occ_count = 1, occ_emit = 1;   // blocks of k_batch_count / k_batch_emit a CU holds (the occupancy query, at most 8): their grids
+        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around the three kernels of a launch (the scan is two launches)
+        u64* in = nullptr;          // [states][W]
+        u32* count = nullptr;       // [states] counts, [states] invariant bits, then nh planes of [states] bitset words
+        u64* offsets = nullptr;     // [states + 1], then the scan's 256 block sums
+        uint64_t states_cap = 0;    // states the three above are sized for
+        u64* rec = nullptr;
+        uint64_t rec_cap = 0;       // records
+    } batch;
     hipModule_t mod_verify = nullptr;       // KMC_VERIFY=1: a second, differently compiled code object whose dry k_expand regenerates every level
     hipFunction_t f_expand_verify = nullptr;
     uint64_t verify_levels = 0;
@@ -219,9 +233,9 @@ extern const char* const KINDS_BASE[9];
 extern const char* const KINDS_KIP320[9];
 extern const char* const KINDS_FIRST[10];
 extern const char* const KINDS_FRL[3];
-extern const char* const MODE_SUFFIX[4];
-extern const char* const MODE_FILE_TAG[4];
-extern const char* const MODE_KERNEL[4];
+extern const char* const MODE_SUFFIX[5];
+extern const char* const MODE_FILE_TAG[5];
+extern const char* const MODE_KERNEL[5];
 int64_t compiler_id_mine();
 int64_t compiler_id_pinned();
 bool validate(const kmc_config& c, KmcLayout* lay, std::string* name, std::string* inst, int layout_mode = -2);
@@ -278,6 +292,9 @@ void comm_release(kmc_handle* h);
 
 // ---- kmc_sim_engine.cpp ----
 void sim_release(kmc_handle* h);   // at kmc_close: the record buffers, the control block, the code object
+
+// ---- kmc_batch_engine.cpp ----
+void batch_release(kmc_handle* h);   // at kmc_close: the staging, the events, the code object
 
 // ---- kmc_engine_open.cpp ----
 uint64_t auto_frontier_capacity(const kmc_handle* h, double budget);

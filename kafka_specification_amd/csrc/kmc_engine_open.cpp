@@ -122,6 +122,7 @@ void kmc_close(kmc_handle* h) {   // (teardown: the HIP results are dropped on p
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     sim_release(h);
+    batch_release(h);
     growth_release(h);
     if (h->mod_verify) (void)hipModuleUnload(h->mod_verify);
     if (h->mod_sh) (void)hipModuleUnload(h->mod_sh);
