@@ -505,6 +505,24 @@ int kmc_simulate(kmc_handle* h, const kmc_sim_config* sim, kmc_sim_result* out);
  * Of `sim` only seed and depth are read.  Fills up to cap entries; *n_out = the walk's states. */
 int kmc_simulate_walk(kmc_handle* h, const kmc_sim_config* sim, uint64_t walk, uint8_t* canon_states, int32_t* kinds,
                       uint32_t* choice, uint32_t* n_enabled, uint64_t cap, uint64_t* n_out);
+/* Walks from start states given as data (k_simulate_from, in k_simulate's code object): the hybrid of a search to level k and
+ * random walks from its frontier, or walks from hand-made states, reachable or not.  `starts` is [n_starts][state_words] in
+ * host memory, the form kmc_frontier_states writes; it is uploaded once per call.  Walk w starts on
+ * s_0 = starts[w mod n_starts]; its key is that of walk w of kmc_simulate, and step t counts from 0 on that start state.
+ * Everything else is the contract above, word for word: candidates in instance order, r_t = kmc_sim_draw(seed, w, t, n_t),
+ * every state checked, s_0 included, the same three ways to end, the same launches, stop rule and witness.  With
+ * starts = {Init} a from-batch is therefore the same set of walks as kmc_simulate's.
+ * Refused: what kmc_simulate refuses; null `starts` or n_starts = 0, and start states of more than KMC_SIM_STARTS_MAX_BYTES
+ * (sub-sample them): KMC_E_ARG; staging that cannot be allocated: KMC_E_NOMEM. */
+#define KMC_SIM_STARTS_MAX_BYTES (1ull << 30)
+int kmc_simulate_from(kmc_handle* h, const kmc_sim_config* sim, const uint64_t* starts, uint64_t n_starts,
+                      kmc_sim_result* out);
+/* kmc_simulate_walk for a walk of kmc_simulate_from.  Read from the last recorded batch when that was a from-batch of the same
+ * seed and depth, holds the walk, and its recorded s_0 equals starts[walk mod n_starts]; else that one walker is re-run in
+ * record mode, with only its row uploaded.  A recorded batch of one call is never read by the other's walk call. */
+int kmc_simulate_from_walk(kmc_handle* h, const kmc_sim_config* sim, const uint64_t* starts, uint64_t n_starts,
+                           uint64_t walk, uint8_t* canon_states, int32_t* kinds, uint32_t* choice,
+                           uint32_t* n_enabled, uint64_t cap, uint64_t* n_out);
 /* The draw: a fixed 64-bit mix of (seed, walk, step) reduced by multiply-high to 0..n-1 (0 for n = 0).  Pure, no handle. */
 uint64_t kmc_sim_draw(uint64_t seed, uint64_t walk, uint32_t step, uint32_t n);
 

@@ -193,6 +193,10 @@ SYMBOLS = [
     ("kmc_simulate", C.c_int, [_H, C.POINTER(KmcSimConfig), C.POINTER(KmcSimResult)]),
     ("kmc_simulate_walk", C.c_int, [_H, C.POINTER(KmcSimConfig), C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("kmc_simulate_from", C.c_int, [_H, C.POINTER(KmcSimConfig), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(KmcSimResult)]),
+    ("kmc_simulate_from_walk", C.c_int, [_H, C.POINTER(KmcSimConfig), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
+                                         C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                         C.c_uint64, C.POINTER(C.c_uint64)]),
     ("kmc_sim_draw", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
     # the front end (csrc/kmc_frontend.cpp): cfg.py, spec_revision.py, format.py and tlc.py are its callers
     ("kmc_cfg_bind", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(KmcConfig)]),

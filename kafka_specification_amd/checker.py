@@ -276,11 +276,18 @@ class ModelChecker:
                                 walks_per_launch=walks_per_launch, record=int(record))
 
     def simulate(self, n_walks: int, depth: int = 100, seed: int = 0, first_walk: int = 0, walks_per_launch: int = 0,
-                 record: bool = False) -> SimulateResult:
-        """n_walks random walks of at most `depth` states from Init; walk w is a pure function of (constants, seed, w)."""
+                 record: bool = False, starts=None) -> SimulateResult:
+        """n_walks random walks of at most `depth` states from Init; walk w is a pure function of (constants, seed, w).
+        starts: an (n, state_words) uint64 array (what frontier_states returns) — walk w starts on starts[w mod n] instead
+        (kmc_simulate_from: search to a level, then walk from its frontier)."""
         sc = self._sim_config(seed, n_walks, depth, first_walk, walks_per_launch, record)
         r = nat.KmcSimResult()
-        nat.check(self._lib.kmc_simulate(self._h, C.byref(sc), C.byref(r)))
+        if starts is None:
+            nat.check(self._lib.kmc_simulate(self._h, C.byref(sc), C.byref(r)))
+        else:
+            starts = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1, self.state_words)
+            nat.check(self._lib.kmc_simulate_from(self._h, C.byref(sc), starts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  starts.shape[0], C.byref(r)))
         names = self.action_names()
         inv_names = nat.invariant_names(self.cfg.model)
         return SimulateResult(
@@ -292,9 +299,10 @@ class ModelChecker:
             violation_count={inv_names[k]: int(r.violation_count[k]) for k in range(4) if inv_names[k] != "?"},
             launches=int(r.launches), seconds_total=float(r.seconds_total), seconds_kernel=float(r.seconds_kernel))
 
-    def walk(self, w: int, depth: int = 100, seed: int = 0) -> list:
+    def walk(self, w: int, depth: int = 100, seed: int = 0, starts=None) -> list:
         """[(action name or None, canonical state bytes, choice, n_enabled)] of walk w: read from the last recorded batch
-        when it holds the walk (same seed and depth), else that one walker is run again."""
+        when it holds the walk (same seed and depth), else that one walker is run again.  starts: as simulate's — walk w of
+        simulate(starts=...) (kmc_simulate_from_walk)."""
         sc = self._sim_config(seed, 1, depth, w, 0, False)
         cap = depth if depth else 100
         states = (C.c_uint8 * (cap * self.canon_bytes))()
@@ -302,7 +310,12 @@ class ModelChecker:
         choice = (C.c_uint32 * cap)()
         n_en = (C.c_uint32 * cap)()
         n = C.c_uint64()
-        nat.check(self._lib.kmc_simulate_walk(self._h, C.byref(sc), w, states, kinds, choice, n_en, cap, C.byref(n)))
+        if starts is None:
+            nat.check(self._lib.kmc_simulate_walk(self._h, C.byref(sc), w, states, kinds, choice, n_en, cap, C.byref(n)))
+        else:
+            starts = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1, self.state_words)
+            nat.check(self._lib.kmc_simulate_from_walk(self._h, C.byref(sc), starts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       starts.shape[0], w, states, kinds, choice, n_en, cap, C.byref(n)))
         names = self.action_names()
         raw = bytes(states)
         cb = self.canon_bytes

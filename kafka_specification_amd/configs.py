@@ -97,6 +97,12 @@ def precompile_list():
     return uniq
 
 
+# k_simulate_from's refill threshold (csrc/kmc_sim.h, KMC_SIM_REFILL_MIN): refill at one free lane, in batches, never.
+# tests/test_gpu_simulate_from.py holds all three to the same walks; a handle's objects are all built under its defines, so
+# `build()` specialises the search's own object (the one kmc_open loads) under them too, not the level-step and enumerator ones.
+SIM_REFILL_VARIANTS = [{"KMC_JIT_DEFINES": f"-DKMC_SIM_REFILL_MIN={n}"} for n in (1, 16, 64)]
+
+
 def precompile_variants():
     """(config, environment) pairs `build()` also specialises: code objects that are only loaded under an environment
     switch — the second build of the differential self-check (KMC_VERIFY) and the fault-injection build the self-check
@@ -198,7 +204,7 @@ def simulate_precompile_list():
     def k(model, N, L, R, E):
         return dict(model=model, n_replicas=N, log_size=L, max_records=R, max_leader_epoch=E)
     small = k("Kip320", 3, 2, 2, 1)
-    return [(small, {}), (small, {"KMC_LAYOUT": "tight"}), (small, {"KMC_LAYOUT": "rm"}),
+    return [(small, {}), (small, {"KMC_LAYOUT": "tight"}), (small, {"KMC_LAYOUT": "rm"})] + [(small, env) for env in SIM_REFILL_VARIANTS] + [
             (k("Kip279", 3, 2, 2, 2), {}), (k("KafkaTruncateToHighWatermark", 3, 2, 2, 2), {}), (k("Kip320FirstTry", 3, 2, 2, 2), {}),
             (k("Kip101", 3, 2, 2, 2), {}), (k("Kip320", 4, 2, 2, 1), {}), (k("Kip320", 7, 1, 1, 0), {}),
             (dict(model="FiniteReplicatedLog", n_replicas=2, log_size=4, n_log_records=2), {}),
@@ -214,6 +220,7 @@ def batch_precompile_list():
         return dict(model=model, n_replicas=N, log_size=L, max_records=R, max_leader_epoch=E)
     return [(k("Kip320", 2, 2, 2, 1), {}), (k("Kip279", 3, 2, 2, 2), {}), (k("Kip320", 3, 2, 2, 1), {}),
             (k("Kip320FirstTry", 3, 2, 2, 2), {}),
+            (k("KafkaTruncateToHighWatermark", 3, 2, 2, 2), {}),   # (the reference walker of tests/test_gpu_simulate_from.py)
             (dict(model="FiniteReplicatedLog", n_replicas=2, log_size=4, n_log_records=2), {}),
             (dict(model="IdSequence", max_id=10), {}),
             ({kk: v for kk, v in HEADLINE.items() if kk != "invariants"}, {}),

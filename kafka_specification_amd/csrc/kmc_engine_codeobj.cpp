@@ -358,6 +358,10 @@ int get_code_object(const kmc_config& cfg, const std::string& arch, std::vector<
             const long sc = expand_vgpr_spills(*code, "kmc_batch_count_" + name);
             spills = spills < 0 || sc < 0 ? -1 : spills > sc ? spills : sc;
         }
+        if (mode == KMC_CODEOBJ_SIM) {   // (likewise: the worse of k_simulate and k_simulate_from)
+            const long sf = expand_vgpr_spills(*code, "kmc_simulate_from_" + name);
+            spills = spills < 0 || sf < 0 ? -1 : spills > sf ? spills : sf;
+        }
         if (waves_forced) break;  // an explicit -DKMC_MIN_WAVES (tuning, bug hunts) is taken as given and never cached as default
         // The guard must not pass by accident: an unreadable spill count, or a kernel that still spills at
         // one wave per SIMD, is a failed specialisation — not a kernel to run and cache.

@@ -127,14 +127,16 @@ struct kmc_handle {
     hipFunction_t f_expand_sh = nullptr, f_expand_en = nullptr;
     // random simulation (kmc_sim_engine.cpp): k_simulate's code object, its control block, and the last recorded batch
     hipModule_t mod_sim = nullptr;
-    hipFunction_t f_sim = nullptr;
+    hipFunction_t f_sim = nullptr, f_sim_from = nullptr;   // k_simulate, k_simulate_from (walks from start states given as data)
     KmcSimCtl* sim_ctl = nullptr;            // device
     KmcSimCtl* sim_ctl_host = nullptr;       // pinned
     u64* sim_rec = nullptr;                  // device: record planes [step][word][column], then the walks' lengths per column
     uint64_t sim_rec_words = 0;              // allocated
-    struct { uint64_t seed = 0, first_walk = 0, walks_done = 0, stride = 0; uint32_t depth = 0; bool valid = false; } sim_batch;
+    struct { uint64_t seed = 0, first_walk = 0, walks_done = 0, stride = 0; uint32_t depth = 0; bool valid = false, from = false; } sim_batch;   // from: a kmc_simulate_from batch
     u64* sim_one = nullptr;                  // device: the same for one walker (kmc_simulate_walk's re-run)
     uint64_t sim_one_words = 0;
+    u64* sim_starts = nullptr;               // device: the start states of kmc_simulate_from, [n_starts][W], uploaded once per call
+    uint64_t sim_starts_words = 0;           // allocated
     // batched successors of states given as data (kmc_batch_engine.cpp): the kernels' code object and the device staging of a launch
     struct kmc_batch_state {
         hipModule_t mod = nullptr;

@@ -9,7 +9,8 @@
 //   invariants; the walk ends at its first violating state, at a state without candidates, or after `depth` states (the last
 //   of those is checked, not expanded).
 // Two layers: a LANE-LOCAL one (the draw, counting the candidates of a state, locating the r-th, its effect: plain integer
-// code that g++ compiles too — tests/sim_emu.cpp) and the WAVE one (k_simulate: one lane per walker, state in registers).
+// code that g++ compiles too — tests/sim_emu.cpp) and the WAVE one (k_simulate: one lane per walker, state in registers; and
+// k_simulate_from: walks from start states given as data, a lane refilled with the next walker when its own has ended).
 #pragma once
 #include "kmc_common.h"
 
@@ -144,6 +145,29 @@ struct KmcSimArgs {
     u32 flags;         // KMC_SIM_FLAG_*
 };
 
+// k_simulate_from's launch: k_simulate's, and the start states.  (A struct of its own: k_simulate's kernarg layout stays as it is.)
+#define KMC_SIM_CHUNK 256u         // consecutive walkers of a launch that one wave walks, one after the other through its 64 lanes
+#ifndef KMC_SIM_REFILL_MIN
+#define KMC_SIM_REFILL_MIN 1       // free lanes at which a wave hands out new walkers (1..64; 64: idle until all 64 are done, as k_simulate).
+                                   // 1: the fastest of 1 / 16 / 64 on walks from a frontier, DESIGN.md 8a (profiles/simulate_from.json)
+#endif
+struct KmcSimFromArgs {
+    KmcSimCtl* ctl;
+    u64* rec;
+    u64* rec_len;
+    u64 rec_stride;
+    u64 rec_col0;
+    u64 seed;
+    u64 first_walk;
+    const u64* starts;   // [n_starts][W] packed states, AoS: walker i of the launch starts on row (row0 + i) mod n_starts
+    u32 n_starts;
+    u32 row0;            // first_walk mod n_starts
+    u32 n;
+    u32 depth;
+    u32 inv_mask;
+    u32 flags;
+};
+
 #ifndef KMC_HOST_EMU
 KMC_DEV u32 kmc_wave_max(u32 x) {
 #pragma unroll
@@ -272,10 +296,171 @@ template <class M> KMC_DEV void kmc_simulate_body(const KmcSimArgs& a) {
     }
 }
 
+template <int W> struct KmcBatchTile;   // kmc_batch.h: 64 rows of an AoS input -> one per lane, through the wave's LDS rows
+KMC_DEV u64 kmc_wave_sum64(u64 x);      // kmc_batch.h
+
+// k_simulate_from.  Walks from start states given as data: walker i of the launch starts on starts[(first_walk + i) mod n_starts]
+// with t = 0 there; everything else is k_simulate's walk.  The work split is its own.  Walks that start deep in a bounded model
+// end after few and unevenly many states, so a lane does not wait for its tile: the launch is cut into chunks of KMC_SIM_CHUNK
+// consecutive walkers, wave v owns chunks v, v + nwaves, ... and sees them end to end as ONE sequence of `total` walkers behind
+// the wave-uniform `cursor`; a lane holds one walker with ITS OWN step counter, key and index.  At the top of every step the
+// wave ballots its free lanes; at KMC_SIM_REFILL_MIN of them (or when none is alive) free lane j takes walker cursor +
+// rank(j) of the sequence, loads its start state and restarts at t = 0.  A fill of all 64 lanes whose walkers are 64
+// consecutive rows of `starts` goes through LDS (KmcBatchTile::load: whole lines in, one state per lane out); a refill of a
+// few lanes loads its rows directly.  The guard block, the draw and the effect walk are k_simulate's, with per-lane t.
+// Counters: taken per kind by ballot popcount; states / longest per lane as a walk ends, ended_early by popcount, all sent to
+// the control block once, at the wave's end.
+template <class M> KMC_DEV void kmc_simulate_from_body(const KmcSimFromArgs& a) {
+    static_assert(KMC_SIM_REFILL_MIN >= 1 && KMC_SIM_REFILL_MIN <= 64, "KMC_SIM_REFILL_MIN: 1..64 lanes");
+    constexpr int W = M::W;
+    using S = KmcSim<M>;
+    using T = KmcBatchTile<W>;
+    __shared__ u64 lds[KMC_WAVES][64 * T::WP];
+    const u32 lane = kmc_lane();
+    const u32 wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 nwaves = gridDim.x * KMC_WAVES;
+    const u32 wave0 = blockIdx.x * KMC_WAVES + wib;
+    const u32 nchunks = (a.n + KMC_SIM_CHUNK - 1u) / KMC_SIM_CHUNK;
+    const bool record = (a.flags & KMC_SIM_FLAG_RECORD) != 0;
+    // the wave's sequence: walker q of it is walker (wave0 + q / CHUNK * nwaves) * CHUNK + q % CHUNK of the launch
+    u32 total = 0;
+    if (wave0 < nchunks) {
+        total = (nchunks - wave0 + nwaves - 1u) / nwaves * KMC_SIM_CHUNK;
+        if ((nchunks - 1u - wave0) % nwaves == 0) total -= nchunks * KMC_SIM_CHUNK - a.n;   // (the launch's last chunk is this wave's)
+    }
+    u32 cursor = 0;              // wave-uniform: walkers of the sequence handed out
+    u64 taken_lane = 0;          // lane k: steps of action kind k
+    u64 early = 0;               // wave-uniform
+    u64 states = 0;              // per lane, as `longest`
+    u32 longest = 0;
+    bool alive = false;
+    u32 rel = 0, t = 0;          // this lane's walker: its index in the launch, the step it stands on
+    u64 key = 0, meta = 0;
+    u64 s[W];
+    M::init(s);                  // (a lane that never gets a walker runs the leaves' code on a real state)
+#pragma clang loop unroll(disable)
+    for (;;) {
+        const u64 fm = __ballot(!alive);
+        const u32 nfree = (u32)__popcll(fm);
+        if (cursor < total && (nfree >= (u32)KMC_SIM_REFILL_MIN || nfree == 64u)) {
+            const u32 take = kmc_min(nfree, total - cursor);
+            const u32 q = cursor + kmc_rank_in(fm);
+            const bool mine = !alive && q < cursor + take;
+            const u32 nrel = (wave0 + q / KMC_SIM_CHUNK * nwaves) * KMC_SIM_CHUNK + q % KMC_SIM_CHUNK;
+            const u32 row = (a.row0 + nrel) % a.n_starts;   // (row0 < 2^27, nrel < 2^25: no wrap of the sum)
+            const u32 r0 = __builtin_amdgcn_readfirstlane(row);
+            if (fm == ~0ull && cursor % KMC_SIM_CHUNK + take <= KMC_SIM_CHUNK && r0 + take <= a.n_starts) {
+                T::load(a.starts + (u64)r0 * (u64)W, 0, take, lds[wib], lane, s);   // lane j: row r0 + j, walker q
+            } else if (mine) {
+#pragma unroll
+                for (int k = 0; k < W; ++k) s[k] = a.starts[(u64)row * (u64)W + k];
+            }
+            t = mine ? 0u : t;
+            rel = mine ? nrel : rel;
+            key = mine ? kmc_sim_key(a.seed, a.first_walk + nrel) : key;
+            meta = mine ? 0ull : meta;
+            alive = alive || mine;
+            cursor += take;
+        }
+        if (__ballot(alive) == 0) break;   // (... and the cursor is exhausted: 64 free lanes would have been filled)
+        const typename M::Pre pre = M::extract(s);
+        const u64 col = a.rec_col0 + rel;
+        if (record && alive) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) a.rec[((u64)t * (W + 1) + k) * a.rec_stride + col] = s[k];
+            a.rec[((u64)t * (W + 1) + W) * a.rec_stride + col] = meta;
+        }
+        const u32 bad = (alive && a.inv_mask) ? M::violated_pre(pre, a.inv_mask) : 0u;
+        if (__ballot(bad != 0)) {
+            if (bad) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (bad >> k & 1u) atomicAdd(&a.ctl->viol_count[k], 1ull);
+                atomicMin(&a.ctl->witness, ((u64)rel << 32) | ((u64)t << 8) | (u64)(bad & 15u));
+            }
+        }
+        bool live = alive && bad == 0 && t + 1u < a.depth;   // goes on to state t + 1
+        if (__ballot(live)) {
+            typename S::Cand c;
+            const u32 n = S::count(pre, s, live ? 1u : 0u, c);
+            const bool stuck = live && n == 0;
+            const u64 sm = __ballot(stuck);
+            if (sm) {
+                early += (u64)__popcll(sm);
+                if (stuck && (a.flags & KMC_SIM_FLAG_DEADLOCK))
+                    atomicMin(&a.ctl->witness, ((u64)rel << 32) | ((u64)t << 8) | (u64)KMC_SIM_DEADLOCK_BIT);
+                live = live && !stuck;
+            }
+            const u32 r = live ? (u32)kmc_sim_draw_key(key, t, n) : 0u;
+            const u32 ci = live ? S::locate(c, r) : (u32)M::NINST;   // (NINST: no leaf is this lane's)
+            u64 nx[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) nx[k] = s[k];
+            int kind = 0;
+            if constexpr (M::KIND_MAJOR) {
+                kmc_static_for<0, M::NSEGS>([&](auto SS) {
+                    constexpr int sg = decltype(SS)::value;
+                    constexpr int K = M::seg_kind(sg);
+                    constexpr u32 lo = (u32)(M::kind_base(K) + M::seg_first(sg)), cnt = (u32)M::seg_count(sg);
+                    const bool mine = ci - lo < cnt;
+                    const u64 m = __ballot(mine);
+                    if (m) {
+                        const u32 b = mine ? ci - (u32)M::kind_base(K) : (u32)M::seg_first(sg);
+                        u32 extra = 0;
+                        u64 tt[W];
+                        M::template apply<K>(pre, s, tt, b, extra);
+#pragma unroll
+                        for (int k = 0; k < W; ++k) nx[k] = mine ? tt[k] : nx[k];
+                        kind = mine ? K : kind;
+                        taken_lane += lane == (u32)K ? (u64)__popcll(m) : 0ull;
+                    }
+                });
+            } else {
+                kmc_static_for<0, M::NINST>([&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    const bool mine = ci == (u32)i;
+                    const u64 m = __ballot(mine);
+                    if (m) {
+                        int kd = 0;
+                        u32 extra = 0;
+                        u64 tt[W];
+                        (void)M::template inst<i>(pre, s, tt, kd, extra);
+#pragma unroll
+                        for (int k = 0; k < W; ++k) nx[k] = mine ? tt[k] : nx[k];
+                        kind = mine ? kd : kind;
+                        taken_lane += lane == (u32)kd ? (u64)__popcll(m) : 0ull;
+                    }
+                });
+            }
+#pragma unroll
+            for (int k = 0; k < W; ++k) s[k] = nx[k];
+            meta = kmc_sim_meta(kind, r, n);
+        }
+        if (alive && !live) {   // the walk ends on state t: its lane is free from the next step on
+            if (record) a.rec_len[col] = (u64)t + 1ull;
+            states += (u64)t + 1ull;
+            longest = t + 1u > longest ? t + 1u : longest;
+        }
+        alive = live;
+        t += 1u;
+    }
+    const u32 lmax = kmc_wave_max(longest);
+    const u64 nstates = kmc_wave_sum64(states);
+    if (lane < (u32)M::NKINDS && taken_lane) atomicAdd(&a.ctl->taken[lane], taken_lane);
+    if (lane == 0) {
+        if (nstates) atomicAdd(&a.ctl->states, nstates);
+        if (early) atomicAdd(&a.ctl->ended_early, early);
+        if (lmax) atomicMax(&a.ctl->longest, (u64)lmax);
+    }
+}
+
 #if KMC_ONLY_MODE == 3
 #define KMC_INSTANTIATE(NAME, ...)                                                                \
     extern "C" __global__ __launch_bounds__(KMC_BLOCK) void kmc_simulate_##NAME(KmcSimArgs a) {   \
         kmc_simulate_body<__VA_ARGS__>(a);                                                        \
+    }                                                                                             \
+    extern "C" __global__ __launch_bounds__(KMC_BLOCK) void kmc_simulate_from_##NAME(KmcSimFromArgs a) { \
+        kmc_simulate_from_body<__VA_ARGS__>(a);                                                   \
     }
 #endif
 #endif  // !KMC_HOST_EMU
